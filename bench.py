@@ -1,6 +1,12 @@
 """bench.py -- env-steps/s of the batched World.step() hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline figure and nothing else: it builds the batch, warms up, times the K steps and prints the
+line (`value`, `ms_per_step`, the `roofline` of those K steps, `rollout_stats`, `tuning`, the per-rank record).  `--full` adds
+every other block listed below, the shard check and the sustained run.  `--dump-outputs DIR` writes what the last timed step
+handed its caller to DIR/<name>.npy (see dump_outputs); the steps before it are a fixed number, so two runs with the same
+arguments step from the same state.
 
 `--gpus N` with N > 1 starts the N ranks ITSELF: this parent process never touches a GPU, checks that N devices are
 visible (exit code 2 otherwise -- it never measures fewer GPUs than asked for) and runs
@@ -15,7 +21,7 @@ All inputs are resident in HBM before the timed region.  Envs shard over GPUs wi
 (weak scaling); the only collective is one RCCL all-reduce of the rollout counters after the timed region.
 
 Prints ONE JSON line (rank 0).  value = agent-steps/s over the whole job (agents x envs x steps / s);
-env-steps/s is reported next to it.  Objects of the line (NOTEBOOK.md section 7):
+env-steps/s is reported next to it.  Objects of the line (NOTEBOOK.md section 7; all but `roofline` with --full only):
   roofline       the dominant kernel of the --steps region (HIP events on the launch stream).  Each step rewrites the
                  same 122.7 MB of rows, which the 256 MB Infinity Cache absorbs: bound = "infinity-cache-absorbed".
   roofline_hbm   the same kernel on a batch whose rows (503 MB per launch) do not fit the Infinity Cache.  Since round 3 such launches
@@ -52,7 +58,10 @@ HBM_PEAK_GBS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 T
 INFINITY_CACHE_BYTES = 256 << 20
 PLACEMENT_CANDIDATES = 4  # arenas tried for the blocks whose rows go to HBM (transient: 4 x 1.4 GB for config 5)
 HBM_REGIME_ENVS = 262144   # rows of one launch: 491 MB > Infinity Cache
-PREROLL_SECONDS = 1.0      # untimed launches that bring the clocks up before the warm-up (reported as preroll_steps)
+PREROLL_STEPS = 192 * 256  # untimed launches (about 1 s at 20 us) that bring the clocks up before the warm-up (reported as preroll_steps):
+                           # a fixed number, so that the timed steps of every run start from the same state
+DUMP_ENVS = 65536          # --dump-outputs: environments (a seeded sample of the batch) whose small per-env buffers are written ...
+DUMP_OBS_ENVS = 4096       # ... and whose observation is (4 096 x 12 x 12 x 13 float32: 31 MB)
 
 
 def host_cores():
@@ -351,16 +360,44 @@ def stepper(bw, offset=0):
     return bw.sampled_stepper(auto_reset=True, seed=SEED, env_offset=offset)
 
 
-def preroll(torch, dev, fn, seconds=PREROLL_SECONDS):
-    """Untimed launches until `seconds` of wall time have passed: the clocks of a fresh box ramp up over the first tens of
+def preroll(torch, dev, fn, steps=PREROLL_STEPS):
+    """`steps` untimed launches, a synchronize after every 256: the clocks of a fresh box ramp up over the first tens of
     milliseconds, and a 20-step timed region is 0.5 ms long."""
-    n, t0 = 0, time.perf_counter()
-    while time.perf_counter() - t0 < seconds:
+    for _ in range(steps // 256):
         for _ in range(256):
             fn()
         torch.cuda.synchronize(dev)
-        n += 256
-    return n
+    return steps // 256 * 256
+
+
+def _sample(n, k):
+    """A fixed, seeded, sorted choice of min(n, k) of n environments."""
+    import numpy as np
+    return np.arange(n) if n <= k else np.sort(np.random.default_rng(SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(bw, out_dir):
+    """What the last step handed its caller (this rank's batch): the buffers of the LLE_BUF_* layout as DIR/<name>.npy, integers
+    as float32 (8 / 16-bit) or float64 (32-bit; 64-bit ones split into two 32-bit halves on a last axis of 2), every array on a
+    seeded sample of DUMP_ENVS environments, the layered observation `obs` (n, C, H, W) on DUMP_OBS_ENVS of them; `envs` and
+    `obs_envs` say which.  About 42 MB for the headline batch."""
+    import numpy as np
+    import torch
+    names = ("pos", "bits", "gems", "beams", "avail", "actions", "err", "evcount", "events", "done", "reward")
+    host = bw.host_buffers(names)
+    envs, obs_envs = _sample(bw.n_envs, DUMP_ENVS), _sample(bw.n_envs, DUMP_OBS_ENVS)
+    out = {"envs": envs.astype(np.float64), "obs_envs": obs_envs.astype(np.float64),
+           "obs": bw.obs[torch.from_numpy(obs_envs).to(bw.device)].cpu().numpy().astype(np.float32)}
+    for name in names:
+        a = host[name][envs]
+        if a.dtype.itemsize == 8:
+            a = a.view(np.uint64)
+            a = np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1).astype(np.uint32)
+        out[name] = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sum(a.nbytes for a in out.values())
 
 
 def measure_config(torch, timer, dev, map_or_text, n_envs, algo_bytes, steps, label, traffic_key=None, fused=None, fill_ceiling=False):
@@ -713,8 +750,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
     ap.add_argument("--envs-per-wave", type=int, default=0, help="0 = library default")
-    ap.add_argument("--sustained-steps", type=int, default=2000, help="launches of the `sustained` block (0 = skip)")
-    ap.add_argument("--config-steps", type=int, default=200, help="launches per secondary configuration")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure as well: the shard check, the sustained block, the fused "
+                         "rollouts, roofline_hbm, the other configurations and paths, cpu_baseline (the options below say which, and how long)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64; rank 0's batch)")
+    ap.add_argument("--sustained-steps", type=int, default=2000, help="launches of the `sustained` block (0 = skip; --full only)")
+    ap.add_argument("--config-steps", type=int, default=200, help="launches per secondary configuration (--full only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--autotune-ms", type=float, default=None,
                     help="GPU time lle_batch_autotune may spend on the headline batch choosing its launch rules (default: what a plain "
@@ -731,6 +773,8 @@ def main():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N ranks that SHARE cuda:0, collectives over gloo: every line of the N > 1 path but RCCL, on a one-GPU box (not a measurement)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the K timed steps and their line, no other block
+        args.sustained_steps, args.no_fused, args.no_configs, args.no_cpu_baseline = 0, True, True, True
 
     under_launcher = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if not under_launcher and (args.gpus > 1 or args.force_spawn):
@@ -790,8 +834,8 @@ def main():
         for t in range(steps):
             w.step(sample=True, auto_reset=True, seed=SEED, t=t, env_offset=env_offset)
         return world_hash(w)
-    check = shard_check(window_hash, n, rank, world, cdev)
-    if rank == 0 and check["status"] != "ok":
+    check = shard_check(window_hash, n, rank, world, cdev) if args.full else None
+    if rank == 0 and check and check["status"] != "ok":
         print(f"bench.py: shard check FAILED: {check}", file=sys.stderr)
 
     # the headline batch is what a user gets from the constructor: since round 5 BatchedWorld autotunes at construction (10 ms by default)
@@ -816,6 +860,8 @@ def main():
     elapsed = allreduce_max(my_wall, cdev) if use_dist else my_wall
     local_stats = bw.stats()
     stats = allreduce_stats(local_stats, cdev) if use_dist else local_stats
+    if args.dump_outputs and rank == 0:  # (before the sustained block steps the batch on)
+        dump_outputs(bw, args.dump_outputs)
 
     sustained = None
     my_s_wall = s_ms = 0.0
@@ -912,8 +958,9 @@ def main():
                          "frac_wall": ALGO_BYTES_PER_ENV_STEP * n / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
                          "rows_MB_per_launch": rows_bytes / 1e6},
             "rollout_stats": stats,
-            "shard_check": dict(check, what="every rank steps the 64 envs at the head of its shard for 8 steps; the ranks all-gather a 64-bit checksum of (pos, bits, "
-                                             "beams, obs) over the run's collective backend; rank 0 recomputes the N windows with the matching env_offset"),
+            **({"shard_check": dict(check, what="every rank steps the 64 envs at the head of its shard for 8 steps; the ranks all-gather a 64-bit checksum of "
+                                                "(pos, bits, beams, obs) over the run's collective backend; rank 0 recomputes the N windows with the matching env_offset")}
+               if check else {}),
             # the launch rules of the headline batch (lle_batch_tuning): chosen by lle_batch_autotune on this batch's own arena when
             # `autotuned`, the library's default rules otherwise; `log` = the trials (us per launch)
             "tuning": tuning,

@@ -102,7 +102,7 @@ def test_rank_count_mismatch_under_the_launcher_is_an_error():
 @pytest.mark.gpu
 def test_one_rank_through_the_launcher_and_rccl():
     steps = 20
-    res = _run("--gpus", "1", "--force-spawn", "--steps", str(steps), "--warmup", "5", "--no-cpu-baseline", "--no-configs",
+    res = _run("--gpus", "1", "--force-spawn", "--full", "--steps", str(steps), "--warmup", "5", "--no-cpu-baseline", "--no-configs",
                "--no-fused", "--sustained-steps", "0")
     assert res.returncode == 0, res.stderr[-3000:]
     out = _one_line(res)
@@ -111,6 +111,29 @@ def test_one_rank_through_the_launcher_and_rccl():
     assert out["rollout_stats"]["agent_steps"] == 4 * 65536 * steps
     assert out["roofline"]["bound"] == "infinity-cache-absorbed" and 0.0 < out["roofline"]["frac"] < 1.0
     assert out["shard_check"]["status"] == "ok" and out["shard_check"]["ranks"] == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run is the headline and nothing else; --dump-outputs writes the last timed step's buffers, the same in two runs."""
+    import numpy as np
+    steps, dumps = 7, []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        res = _run("--gpus", "1", "--steps", str(steps), "--warmup", "3", "--dump-outputs", str(d))
+        assert res.returncode == 0, res.stderr[-3000:]
+        out = _one_line(res)
+        assert out["steps"] == steps and out["rollout_stats"]["env_steps"] == 65536 * steps and out["ms_per_step"] > 0
+        assert out["unit"] == "agent-steps/s" and out["higher_is_better"] is True and out["dtype"] == "u8" and out["value"] > 0
+        assert not {"cpu_baseline", "sustained", "configs", "fused_rollout", "shard_check"} & set(out)
+        arrays = {f.stem: np.load(f) for f in sorted(d.glob("*.npy"))}
+        assert {"obs", "pos", "actions", "reward", "done"} <= set(arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["obs"].shape[1:] == (12, 12, 13) and arrays["actions"].shape[1] == 4
+        dumps.append(arrays)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
 
 
 @pytest.mark.gpu
@@ -147,7 +170,7 @@ def test_two_rank_code_path_rehearsed_on_one_gpu():
     region, max over ranks, counter all-reduce, per-rank gather, the one JSON line) except RCCL itself, which refuses two
     ranks on one device.  Not a measurement, and the line says so."""
     steps = 20
-    res = _run("--gpus", "2", "--rehearse-on-one-gpu", "--steps", str(steps), "--warmup", "5", "--no-cpu-baseline", "--no-configs",
+    res = _run("--gpus", "2", "--rehearse-on-one-gpu", "--full", "--steps", str(steps), "--warmup", "5", "--no-cpu-baseline", "--no-configs",
                "--fused-steps", "4", "--sustained-steps", "40")
     assert res.returncode == 0, res.stderr[-3000:]
     out = _one_line(res)

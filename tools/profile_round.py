@@ -1,9 +1,9 @@
 """profile_round.py -- the round's measured evidence in one go (runs on the GPU box: `gpurun -- python3 tools/profile_round.py r02`).
 
-  1. `python3 bench.py`                                               -> gpurun_out/prof/bench.json
-  2. `rocprofv3 --kernel-trace --stats -- python3 bench.py ...`       -> per (kernel, grid) launch durations
-  3. `rocprofv3 --pmc WRITE_SIZE --kernel-trace -- python3 bench.py`  -> bytes written per launch (L2 -> fabric)
-  4. `rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python3 bench.py`  -> bytes fetched per launch (x2 on gfx950)
+  1. `python3 bench.py --full`                                        -> prof/bench.json of the output folder
+  2. `rocprofv3 --kernel-trace --stats -- python3 bench.py --full ...`  -> per (kernel, grid) launch durations
+  3. `rocprofv3 --pmc WRITE_SIZE --kernel-trace -- python3 bench.py --full ...`  -> bytes written per launch (L2 -> fabric)
+  4. `rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python3 bench.py --full ...`  -> bytes fetched per launch (x2 on gfx950)
      (counters in passes of their own, with --kernel-trace only: MI355X_MICROARCH.md, HBM / rocprofv3 section)
 and writes profiles/<tag>_summary.md, profiles/<tag>_kernel_stats.csv and profiles/traffic.json (read by bench.py).
 
@@ -57,10 +57,10 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     for d in ("stats", "pmc_write", "pmc_fetch"):
         subprocess.run(["rm", "-rf", os.path.join(OUT, d)])
-    res = run([sys.executable, BENCH], "bench.err")
+    res = run([sys.executable, BENCH, "--full"], "bench.err")
     bench = json.loads(res.stdout.strip().splitlines()[-1])
     json.dump(bench, open(os.path.join(OUT, "bench.json"), "w"))
-    light = ["--no-cpu-baseline", "--steps", "200", "--sustained-steps", "0", "--config-steps", "60"]
+    light = ["--full", "--no-cpu-baseline", "--steps", "200", "--sustained-steps", "0", "--config-steps", "60"]
     res = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(OUT, "stats"), "--", sys.executable, BENCH] + light,
               "stats.err")
     bench_prof = json.loads(res.stdout.strip().splitlines()[-1])
