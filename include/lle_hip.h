@@ -183,6 +183,12 @@ int lle_map_row_head_env_sources_second(const lle_map* map, int32_t* first_byte,
  * of the env's LLE_BUF_BEAMS record (word == laser_id, bit == offset unless a beam of the map is longer than 32 cells). */
 typedef struct lle_laser_tile { int32_t i, j, laser_id, offset, layer, word, bit; } lle_laser_tile;
 int lle_map_laser_tiles(const lle_map* map, lle_laser_tile* out, int cap);
+/* EVERY layer of every laser cell, outermost first (depth 0), cells in row-major order: the wrapped stack a renderer
+ * recurses through (Laser::wrapped, src/core/tiles/laser.rs; draw_laser, src/rendering/renderer.rs:187-198), where
+ * lle_map_laser_tiles stops at the second layer.  `direction` is the beam's (that of its source, N=0 E=1 S=2 W=3).
+ * Writes up to `cap` entries; returns the total count (or a negative status).  Host side. */
+typedef struct lle_cell_layer { int32_t i, j, depth, laser_id, offset, direction, word, bit; } lle_cell_layer;
+int lle_map_cell_layers(const lle_map* map, lle_cell_layer* out, int cap);
 
 /* World.world_string (pyworld.rs:212-218): v1 text with the current source colours.  Returns needed size. */
 size_t lle_map_world_string(const lle_map* map, char* buf, size_t cap);

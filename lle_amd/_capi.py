@@ -37,7 +37,7 @@ PARSE_ERROR_NAMES = {
 EXPORTS = [
     "lle_abi_version", "lle_last_status", "lle_last_error", "lle_action_hash",
     "lle_map_parse", "lle_map_level", "lle_map_free", "lle_map_get_info", "lle_map_positions", "lle_map_sources",
-    "lle_map_set_source", "lle_map_set_exits", "lle_map_clone", "lle_map_colour_allowed", "lle_map_reset_beam", "lle_map_set_row_align", "lle_map_set_head_lines", "lle_map_row_head", "lle_map_row_head_env_sources", "lle_map_row_head_env_sources_second", "lle_map_row_dynamic_lines", "lle_map_laser_tiles", "lle_map_world_string",
+    "lle_map_set_source", "lle_map_set_exits", "lle_map_clone", "lle_map_colour_allowed", "lle_map_reset_beam", "lle_map_set_row_align", "lle_map_set_head_lines", "lle_map_row_head", "lle_map_row_head_env_sources", "lle_map_row_head_env_sources_second", "lle_map_row_dynamic_lines", "lle_map_laser_tiles", "lle_map_cell_layers", "lle_map_world_string",
     "lle_batch_arena_bytes", "lle_batch_create", "lle_batch_arena_bytes_multi", "lle_batch_create_multi", "lle_batch_n_maps", "lle_batch_free", "lle_batch_get_buffer", "lle_batch_n_envs",
     "lle_batch_reset", "lle_batch_step", "lle_batch_rollout", "lle_batch_set_state", "lle_batch_update_sources", "lle_batch_update_map", "lle_batch_observe",
     "lle_batch_snapshot_bytes", "lle_batch_snapshot", "lle_batch_restore",
@@ -76,6 +76,11 @@ class SourceInfo(C.Structure):
 
 class LaserTile(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("i", "j", "laser_id", "offset", "layer", "word", "bit")]
+
+
+class CellLayer(C.Structure):
+    """lle_cell_layer (include/lle_hip.h): one layer of a laser cell's stack, outermost first."""
+    _fields_ = [(n, C.c_int32) for n in ("i", "j", "depth", "laser_id", "offset", "direction", "word", "bit")]
 
 
 class EnvOutputs(C.Structure):
@@ -165,6 +170,8 @@ def lib():
     L.lle_map_row_head_env_sources_second.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.lle_map_laser_tiles.restype = i32
     L.lle_map_laser_tiles.argtypes = [vp, C.POINTER(LaserTile), i32]
+    L.lle_map_cell_layers.restype = i32
+    L.lle_map_cell_layers.argtypes = [vp, C.POINTER(CellLayer), i32]
     L.lle_map_world_string.restype = C.c_size_t
     L.lle_map_world_string.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.lle_batch_arena_bytes.restype = i64
@@ -382,6 +389,13 @@ class Map:
         n = lib().lle_map_laser_tiles(self.h, None, 0)
         arr = (LaserTile * max(n, 1))()
         lib().lle_map_laser_tiles(self.h, arr, n)
+        return [arr[k] for k in range(n)]
+
+    def cell_layers(self):
+        """Every layer of every laser cell, outermost first (lle_map_cell_layers): the stack a renderer recurses through."""
+        n = lib().lle_map_cell_layers(self.h, None, 0)
+        arr = (CellLayer * max(n, 1))()
+        lib().lle_map_cell_layers(self.h, arr, n)
         return [arr[k] for k in range(n)]
 
     def colour_allowed(self, laser_id, agent_id):

@@ -211,6 +211,8 @@ class BatchedWorld:
             setattr(self, "stats_blocks" if name == "stats" else name, t)
 
     def __del__(self):
+        for r in getattr(self, "_renderers", {}).values():
+            r.free()
         h = getattr(self, "h", None)
         if h:
             try:
@@ -370,11 +372,61 @@ class BatchedWorld:
     def update_sources(self):
         """Push self.map's current source colours / enabled flags to the device (LaserSource.enable/disable/set_colour)."""
         self._check(_capi.lib().lle_batch_update_sources(self.h, self.map.h, self._stream()))
+        self._refresh_renderers(0)
 
     def update_map(self, map_index=0):
         """Push self.maps[map_index] to the device after Map.set_exits (World.exit_pos = ...) or Map.set_source: tables,
         reset states and the observation follow, the dynamic state of live envs stays (lle_batch_update_map)."""
         self._check(_capi.lib().lle_batch_update_map(self.h, int(map_index), self.maps[map_index].h, self._stream()))
+        self._refresh_renderers(map_index)
+
+    # ---- rendering (the reference's World.get_image, src/rendering/renderer.rs; lle_amd.rendering)
+    _RENDER_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}
+
+    def _renderer(self, atlas):
+        """The renderer of `atlas` (None: the built-in sprites) over this batch, created on first use: its static tables are
+        uploaded once and refreshed by update_map / update_sources / set_exits.  Keyed by the atlas's CONTENT (SpriteAtlas.digest):
+        two atlases with the same sprites -- SpriteAtlas.from_directory(p) called twice -- share one renderer."""
+        from . import rendering
+        if not hasattr(self, "_renderers"):
+            self._renderers = {}
+        key = None if atlas is None or atlas is rendering.SpriteAtlas.builtin() else atlas.digest
+        r = self._renderers.get(key)
+        if r is None:
+            r = self._renderers[key] = rendering.Renderer(self, atlas)
+        return r
+
+    def _refresh_renderers(self, map_index):
+        for r in getattr(self, "_renderers", {}).values():
+            r.update_map(map_index, self.maps[map_index], self._stream())
+
+    def render_desc(self, n_sel=None, dtype=torch.uint8, atlas=None):
+        """Shape / strides (elements) / bytes of render()'s output for n_sel environments (lle_render_desc)."""
+        return self._renderer(atlas).desc(self.n_envs if n_sel is None else n_sel, self._RENDER_DTYPES[dtype])
+
+    def render(self, env_ids=None, out=None, dtype=torch.uint8, atlas=None):
+        """World.get_image (pyworld.rs:518-524) of every env, or of `env_ids` (integers; slot s of the output = env env_ids[s]),
+        in ONE launch of the render kernel on the current stream: a (n_sel, 32H+1, 32W+1, 3) strided view (each frame at a pitch
+        of whole 128-byte lines) of `out` (a uint8 device buffer of render_desc(n_sel, dtype).bytes bytes; allocated when None).
+        dtype: torch.uint8 (the reference's), or float16 / bfloat16 / float32 widened at the store -- the same values.
+        atlas: a rendering.SpriteAtlas (None: the package's own sprites; SpriteAtlas.from_directory for the reference's art).
+        After set_sources every env is drawn with ITS source colours (LLE_BUF_SRC_COLOUR)."""
+        r = self._renderer(atlas)
+        ids_ptr, n_sel = None, self.n_envs
+        if env_ids is not None:
+            env_ids = torch.as_tensor(env_ids, dtype=torch.int64).to(self.device).contiguous().view(-1)
+            ids_ptr, n_sel = env_ids.data_ptr(), int(env_ids.numel())
+        code = self._RENDER_DTYPES[dtype]
+        d = r.desc(n_sel, code)
+        if out is None:
+            out = torch.empty(int(d.bytes) + 256, dtype=torch.uint8, device=self.device)
+            out = out[(-out.data_ptr()) % 256:][: int(d.bytes)]
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= d.bytes and out.data_ptr() % 16 == 0
+        flags = 1 if getattr(self, "_env_sources", False) else 0  # LLE_RENDER_ENV_SOURCES
+        r.frame(ids_ptr, n_sel, flags, code, out.data_ptr(), out.numel(), self._stream())
+        self._render_ids = env_ids  # (kept alive until the launch has read it)
+        flat = out[: int(d.bytes)].view(dtype)
+        return torch.as_strided(flat, [int(d.shape[k]) for k in range(4)], [int(d.stride[k]) for k in range(4)])
 
     def set_exits(self, exits, map_index=0):
         """World.exit_pos = exits for every env of map `map_index` (src/core/world.rs:195-234)."""
@@ -407,6 +459,7 @@ class BatchedWorld:
         else:
             assert write_obs, "lle_batch_set_sources always rewrites the observation"
             self._check(_capi.lib().lle_batch_set_sources(self.h, cp, ep, mp, self._stream()))
+        self._env_sources = True  # from now on every env has its own sources (render() reads LLE_BUF_SRC_COLOUR)
 
     def observe(self):
         self._check(_capi.lib().lle_batch_observe(self.h, self._stream()))

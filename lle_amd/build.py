@@ -6,13 +6,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def build_native(force=False, verbose=False):
-    csrc = os.path.join(_HERE, "csrc")
-    cmd = ["make", "-C", csrc, "-j8"] + (["-B"] if force else [])
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if verbose or res.returncode != 0:
-        print(res.stdout)
-    if res.returncode != 0:
-        raise RuntimeError("building liblle_hip.so failed (hipcc --offload-arch=gfx950)")
+    """liblle_hip.so (lle_amd/csrc), then liblle_render.so (lle_amd/render: the renderer, linked against the first)."""
+    for src, lib in (("csrc", "liblle_hip.so"), ("render", "liblle_render.so")):
+        cmd = ["make", "-C", os.path.join(_HERE, src), "-j8"] + (["-B"] if force else [])
+        res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if verbose or res.returncode != 0:
+            print(res.stdout)
+        if res.returncode != 0:
+            raise RuntimeError(f"building {lib} failed (hipcc --offload-arch=gfx950)")
     return os.path.join(_HERE, "liblle_hip.so")
 
 

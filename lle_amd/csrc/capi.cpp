@@ -421,6 +421,23 @@ int lle_map_laser_tiles(const lle_map* map, lle_laser_tile* out, int cap) {
     return n;
 }
 
+int lle_map_cell_layers(const lle_map* map, lle_cell_layer* out, int cap) {
+    if (!map) return fail(LLE_ERR_NULL, "NULL map");
+    const Map& m = map->m;
+    int n = 0;
+    for (int c = 0; c < m.H * m.W; c++) {
+        const auto& layers = m.cell_layers[c];
+        for (int k = 0; k < (int)layers.size(); k++) {
+            if (out && n < cap) {
+                const int lid = layers[k].laser_id, off = layers[k].offset;
+                out[n] = lle_cell_layer{c / m.W, c % m.W, k, lid, off, m.sources[(size_t)lid].direction, m.word_of(lid, off), Map::bit_of(off)};
+            }
+            n++;
+        }
+    }
+    return n;
+}
+
 size_t lle_map_world_string(const lle_map* map, char* buf, size_t cap) {
     if (!map) return 0;
     std::string s = map->m.world_string();

@@ -4,8 +4,8 @@ The reference's `LLE` (python/lle/env/env.py:39-255) is a thin host class around
 strategy, `compute_done`, observation / state generators, `available_actions` (optionally without moves into foreign
 lasers), `randomize_lasers` on reset.  Every one of those pieces already runs on the GPU behind the C ABI
 (include/lle_hip.h); this class strings them together with the reference's argument names and meanings and returns
-device tensors with a leading env axis.  No marlenv dependency, no extras generators, no PBRS shaping and no rendering
- -- the hot path and its immediate callers only.
+device tensors with a leading env axis.  No marlenv dependency, no extras generators and no PBRS shaping (SURVEY.md
+section 9) -- the hot path and its immediate callers only; "rgb-image" frames come from the render kernel (lle_amd.rendering).
 
     env = BatchedLLE(Map(level=6), 65536, obs_type="layered", randomize_lasers=True)
     obs, state = env.reset()
@@ -41,6 +41,7 @@ _OBS_KINDS = {
     "layered-padded-1": (_capi.LLE_OBS_LAYERED_PADDED, 1), "layered-padded-2": (_capi.LLE_OBS_LAYERED_PADDED, 2),
     "layered-padded-3": (_capi.LLE_OBS_LAYERED_PADDED, 3),
 }
+_RGB_IMAGE = -1  # the kind of "rgb-image": frames of the render kernel (BatchedWorld.render), not an lle_batch_observe_as kind
 
 
 class BatchedLLE:
@@ -68,6 +69,8 @@ class BatchedLLE:
         if obs_dtype is not None and all(k[0] in (_capi.LLE_OBS_STATE, _capi.LLE_OBS_NORMALIZED_STATE) for k in (self._obs_kind, self._state_kind)):
             raise ValueError("obs_dtype is the element type of the layered-style observations: obs_type and state_type are both state vectors")
         self.world = BatchedWorld(maps, n_envs, device=device, obs_dtype=obs_dtype)
+        # "rgb-image": uint8 frames (the reference's), or widened at the store to the obs_dtype asked for
+        self._render_dtype = self.world.obs_dtype if obs_dtype is not None and self.world.obs_dtype != torch.int8 else torch.uint8
         self.n_envs, self.n_agents, self.n_actions = self.world.n_envs, self.world.map.n_agents, 5
         # the step kernel's own (layered) observation is only written when somebody reads it
         self._needs_layered = _capi.LLE_OBS_LAYERED in (self._obs_kind[0], self._state_kind[0])
@@ -109,7 +112,7 @@ class BatchedLLE:
         if name == "layered-padded":
             return (_capi.LLE_OBS_LAYERED_PADDED, int(padding_size))
         if name == "rgb-image":
-            raise NotImplementedError("rendering is outside the scope of lle_amd (SURVEY.md section 2, row 11)")
+            return (_RGB_IMAGE, 0)
         try:
             return _OBS_KINDS[name]
         except KeyError:
@@ -166,6 +169,9 @@ class BatchedLLE:
         m, A = self.world.map, self.n_agents
         if k in (_capi.LLE_OBS_STATE, _capi.LLE_OBS_NORMALIZED_STATE):
             return [3 * A + m.n_gems]
+        if k == _RGB_IMAGE:  # (RGBImage.shape is the frame; the observation tiles it per agent, the state is agent 0's)
+            frame = [32 * m.height + 1, 32 * m.width + 1, 3]
+            return frame if state else [A] + frame
         d = self.world.obs_desc(k, p)
         shape = [int(d.shape[i]) for i in range(1, d.ndim)]
         if state and k in (_capi.LLE_OBS_PARTIAL, _capi.LLE_OBS_PERSPECTIVE):
@@ -213,7 +219,7 @@ class BatchedLLE:
         if seed is not None:
             self.seed(seed)
         self._reset_world(env_mask, colours)
-        return self.get_observation(), self.get_state()
+        return self._obs_and_state()
 
     def _reset_world(self, env_mask, colours=None, write_obs=True):
         """world.reset() and, with randomize_lasers, the recolouring of the same envs: one launch either way
@@ -250,14 +256,47 @@ class BatchedLLE:
         k, p = kind
         if k == _capi.LLE_OBS_LAYERED:
             return self.world.obs  # written by the step / reset / set_sources kernel itself
+        if k == _RGB_IMAGE:
+            return self.world.render(dtype=self._render_dtype)  # (n, 32H+1, 32W+1, 3): one launch of the render kernel
         return self.world.observe_as(k, p)
+
+    def get_image(self, env=0):
+        """LLE.get_image (python/lle/env/env.py:250-251) of environment `env`: numpy uint8 (32H+1, 32W+1, 3)."""
+        img = self.world.render(env_ids=[int(env)])[0]
+        torch.cuda.synchronize(self.world.device)
+        return img.cpu().numpy()
+
+    def _bound_render(self):
+        """A zero-argument callable rendering every env into ONE persistent buffer (`call.out`, overwritten by every call)."""
+        w, dt = self.world, self._render_dtype
+        d = w.render_desc(dtype=dt)
+        buf = torch.empty(int(d.bytes) + 256, dtype=torch.uint8, device=w.device)
+        buf = buf[(-buf.data_ptr()) % 256:][: int(d.bytes)]
+
+        def call():
+            return w.render(out=buf, dtype=dt)
+        call.out = torch.as_strided(buf.view(dt), [int(d.shape[q]) for q in range(4)], [int(d.stride[q]) for q in range(4)])
+        return call
+
+    def _bind_observer(self, kind):
+        return self._bound_render() if kind[0] == _RGB_IMAGE else self.world.bound_observer(*kind)
 
     def get_observation(self):
         """The observation of every env with the reference's per-env shape behind the env axis.  Kinds whose agents all
         see the same tensor carry ONE copy (the reference tiles it n_agents times, observations.py:151,266):
         broadcast with `.unsqueeze(1).expand(-1, n_agents, ...)` if the learner wants the tiled layout."""
         obs = self._observe(self._obs_kind)
+        if self._obs_kind[0] == _RGB_IMAGE:  # (n, A, 32H+1, 32W+1, 3): the frame broadcast over the agents (observations.py:183-185)
+            return obs.unsqueeze(1).expand(-1, self.n_agents, -1, -1, -1)
         return obs.flatten(1) if self.obs_type == "flattened" else obs
+
+    def _obs_and_state(self, state=None):
+        """(get_observation(), get_state()) -- or `state` when the caller already has it.  With obs_type == state_type == "rgb-image"
+        ONE render launch serves both: the state is the frame, the observation the same frame broadcast over the agents."""
+        if state is None and self._obs_kind[0] == _RGB_IMAGE and self._state_kind == self._obs_kind:
+            frame = self._observe(self._obs_kind)
+            return frame.unsqueeze(1).expand(-1, self.n_agents, -1, -1, -1), frame
+        return self.get_observation(), (state if state is not None else self.get_state())
 
     def get_state(self):
         """LLE.get_state (env.py:205-206): the state generator's observation of agent 0."""
@@ -362,7 +401,7 @@ class BatchedLLE:
                 if t["state"] is None and self.state_type == "flattened":
                     state = state.flatten(1)
             else:
-                obs, state = self.get_observation(), (t["state"] if t["state"] is not None else self.get_state())
+                obs, state = self._obs_and_state(t["state"])
             return {"obs": obs, "state": state, "reward": t["reward"],
                     "done": self.done, "available_actions": t["available"].view(torch.bool), "err": w.err}
         return self._outputs()
@@ -381,9 +420,9 @@ class BatchedLLE:
                 b["outs"] = (t, w.bound_env_outputs(state=t["state"], normalize_state=self._state_kind[0] == _capi.LLE_OBS_NORMALIZED_STATE,
                                                     reward=t["reward"], multi_objective=self.multi_objective, available=t["available"],
                                                     walkable_lasers=self.walkable_lasers))
-                b["obs"] = None if self._obs_kind[0] == _capi.LLE_OBS_LAYERED else w.bound_observer(*self._obs_kind)
+                b["obs"] = None if self._obs_kind[0] == _capi.LLE_OBS_LAYERED else self._bind_observer(self._obs_kind)
                 b["state"] = None if plain_state or self._state_kind[0] == _capi.LLE_OBS_LAYERED else (
-                    b["obs"] if self._state_kind == self._obs_kind and b["obs"] is not None else w.bound_observer(*self._state_kind))
+                    b["obs"] if self._state_kind == self._obs_kind and b["obs"] is not None else self._bind_observer(self._state_kind))
             recolour = auto_reset and self._recolour_in_step
             in_kernel_reset = auto_reset and (recolour or not self.randomize_lasers)
             b[key] = w.bound_step(auto_reset=in_kernel_reset, recolour_resets=recolour, write_obs=self._needs_layered, seed=self._seed_value,
@@ -398,6 +437,8 @@ class BatchedLLE:
         obs = w.obs if b["obs"] is None else b["obs"]()
         if self.obs_type == "flattened":
             obs = obs.flatten(1)
+        if self._obs_kind[0] == _RGB_IMAGE:
+            obs = obs.unsqueeze(1).expand(-1, self.n_agents, -1, -1, -1)
         if t["state"] is not None:
             state = t["state"]
         elif b["state"] is None:
@@ -423,8 +464,8 @@ class BatchedLLE:
         avail = torch.empty((n, self.n_agents, 5), dtype=torch.uint8, device=dev)
         w.env_outputs(state=state, normalize_state=self._state_kind[0] == _capi.LLE_OBS_NORMALIZED_STATE, reward=reward,
                       multi_objective=self.multi_objective, available=avail, walkable_lasers=self.walkable_lasers)
-        return {"obs": self.get_observation(), "state": state if fused_state else self.get_state(), "reward": reward,
-                "done": self.done, "available_actions": avail.view(torch.bool), "err": w.err}
+        obs, state = self._obs_and_state(state if fused_state else None)
+        return {"obs": obs, "state": state, "reward": reward, "done": self.done, "available_actions": avail.view(torch.bool), "err": w.err}
 
 
 class Builder:

@@ -4,8 +4,8 @@ Every tensor comes from a HIP kernel reading the world's device state (layered: 
 kinds: lle_amd/csrc/observers.hip behind `lle_batch_observe_as`).  The classes below only give those tensors the
 reference's protocol -- class names, the channel attributes (`A0`, `LASER_0`, `WALL`, ...), `shape`, `obs_type`,
 `observe()` as float32 with the (n_agents, ...) leading axis, `to_world_state` -- so that code written against
-`ObservationType(...).get_observation_generator(world)` runs unchanged.  "rgb-image" (rendering) is out of scope
-(SURVEY.md section 2 row 11).
+`ObservationType(...).get_observation_generator(world)` runs unchanged.  "rgb-image" is the frame of the render kernel
+(lle_amd/render/render.hip through World.get_image).
 """
 from enum import Enum
 from typing import Literal
@@ -44,9 +44,8 @@ class ObservationType(str, Enum):
 
     def get_observation_generator(self, world, padding_size=0):
         """Same dispatch as python/lle/observations.py:66-97, as a table."""
-        if self is ObservationType.RGB_IMAGE:
-            raise NotImplementedError("rendering is outside the scope of lle_amd (SURVEY.md section 2, row 11)")
         make = {
+            "rgb-image": lambda: RGBImage(world),
             "normalized-state": lambda: StateGenerator(world, normalize=True),
             "state": lambda: StateGenerator(world, normalize=False),
             "layered": lambda: Layered(world),
@@ -194,6 +193,21 @@ class PartialGenerator(ObservationGenerator):
         self._center = square_size // 2
         self.WALL, self.LASER_0, self.GEM, self.EXIT = a, a + 1, 2 * a + 1, 2 * a + 2
         self._shape = (2 * a + 3, square_size, square_size)
+
+
+class RGBImage(ObservationGenerator):
+    """The rendered world (python/lle/observations.py:178-194): float32 (A, 32H+1, 32W+1, 3), the frame of World.get_image (the
+    render kernel of liblle_render.so) once per agent -- the reference's np.tile, served as a broadcast view."""
+
+    _obs_type = ObservationType.RGB_IMAGE
+
+    def __init__(self, world):
+        super().__init__(world)
+        self._shape = (32 * world.height + 1, 32 * world.width + 1, 3)
+
+    def observe(self):
+        img = self._world.get_image().astype(np.float32)
+        return np.broadcast_to(img, (self._world.n_agents,) + img.shape)
 
 
 class AgentZeroPerspective(Layered):

@@ -9,12 +9,17 @@ For throughput use `lle_amd.BatchedWorld`; this facade pays one kernel launch + 
 import copy
 import itertools
 import os
+import sys
 from enum import Enum
 
 import numpy as np
 
-from . import _capi, _decode
+from . import _capi, _decode, rendering
 from ._capi import LLE_POS_EXIT, LLE_POS_GEM, LLE_POS_START, LLE_POS_VOID, LLE_POS_WALL, Map, MapParseError
+
+# the reference's import path `lle.world.rendering` (python/lle/world/rendering/__init__.pyi: TILE_SIZE) is a submodule of its world
+# package; here `world` is a module, so `lle_amd.world.rendering` is registered as an alias of lle_amd.rendering
+sys.modules.setdefault(__name__ + ".rendering", rendering)
 
 
 # ------------------------------------------------------------------------------------------------ exceptions
@@ -669,7 +674,13 @@ class World:
         return (32 * self.width + 1, 32 * self.height + 1)  # src/unit_tests/test_renderer.rs:24
 
     def get_image(self):
-        raise NotImplementedError("rendering is outside the scope of lle_amd (SURVEY.md section 2, row 11)")
+        """Render the world (pyworld.rs:518-524): numpy uint8 (32 H + 1, 32 W + 1, 3), drawn by the render kernel of
+        liblle_render.so with the package's own sprites (lle_amd.rendering says how its frames differ from the reference's)."""
+        import torch
+        b = self._batch
+        img = b.render()[0]
+        torch.cuda.synchronize(b.device)
+        return img.cpu().numpy()
 
     def layered_observation(self):
         """(C, H, W) float32 layered observation of the current state (python/lle/observations.py:254-266), from the GPU: the
