@@ -17,8 +17,17 @@ DEFAULT_ENGINE = ["env"]  # tests/test_hostsim_lanes.py reruns the CPU suites wi
 
 
 def build():
+    """Compile libhostsim.so when it is missing or older than its sources.  Several processes may get here at once (the two gloo ranks
+    of tests/test_distributed_gloo.py on a fresh checkout): each links into a file of its own and renames it into place, so nobody
+    ever opens a half-written library."""
     if not os.path.exists(_LIB) or any(os.path.getmtime(_LIB) < os.path.getmtime(d) for d in _DEPS):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", _LIB] + _SRCS)
+        tmp = os.path.join(_HERE, f"libhostsim.{os.getpid()}.so")
+        try:
+            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", tmp] + _SRCS)
+            os.replace(tmp, _LIB)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
     return _LIB
 
 

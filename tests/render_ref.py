@@ -168,3 +168,145 @@ def states_of(bw, env_sources=False):
     colours = bw.src_colour.cpu().numpy() if env_sources else None
     return [State([(int(p[0]), int(p[1])) for p in pos[e]], int(gems[e]), list(beams[e]), None if colours is None else list(colours[e]))
             for e in range(bw.n_envs)]
+
+
+# ---- synthetic states: the domain of the render kernel beyond what rollouts reach (tests/test_gpu_render_states.py)
+def cell_tags(scene):
+    """(i, j) -> the set of classes a cell belongs to, for the coverage assertions: its static tile ("floor", "wall", "exit",
+    "void"; a source's cell is "source"), "gem", and "beamK" for a stack of K laser layers.  "floor" means a bare floor cell."""
+    tags = {(i, j): {"floor"} for i in range(scene.height) for j in range(scene.width)}
+    for name, cells in (("wall", scene.walls), ("exit", scene.exits), ("void", scene.voids)):
+        for c in cells:
+            tags[tuple(c)] = {name}
+    for s in scene.sources:
+        tags[(s[0], s[1])] = {"source"}
+    for c in scene.gems:
+        tags[tuple(c)].add("gem")
+    for c, stack in scene.stacks.items():
+        tags[tuple(c)].add(f"beam{len(stack)}")
+    for c, t in tags.items():
+        if "floor" in t and len(t) > 1:
+            t.discard("floor")
+    return tags
+
+
+def random_states(scenes, n_envs, n_agents, n_words, seed, planted=()):
+    """Seeded states over the whole domain the kernel reads, as numpy arrays for `write_states`: pos u8 [n, A, 2], gems u32 [n],
+    beams u32 [n, Lw], colours u8 [n, Lw].  scenes: the Scene of every block of envs (len(scenes) divides n_envs).
+      gems    any subset (random 32-bit words masked to the map's gems); env 0 none, env 1 all, env 2 the highest index alone
+      beams   arbitrary words, not only prefixes; env 0 all off, env 1 all on, envs 2 .. 33 bit (e - 2) of EVERY word alone,
+              then single bits of single words and random words
+      pos     any cell that is not a laser source: the class of the cell (cell_tags) is drawn first so that rare classes are hit,
+              then a cell of it; an agent joins an earlier agent's cell with probability 1/4; env 3: all agents on one cell
+      colours any byte; 0, the values around 12 and 255 are frequent
+    `planted`: (env, agent, (i, j)) positions put in afterwards.  `classes_hit` says which classes of cells the agents stand on."""
+    rng = np.random.default_rng(seed)
+    per = n_envs // len(scenes)
+    pos = np.zeros((n_envs, n_agents, 2), np.uint8)
+    gems = rng.integers(0, 1 << 32, n_envs, dtype=np.uint64).astype(np.uint32)
+    beams = rng.integers(0, 1 << 32, (n_envs, max(n_words, 1)), dtype=np.uint64).astype(np.uint32)
+    palette = np.array([0, 1, 2, 3, 4, 5, 11, 12, 13, 14, 200, 254, 255], np.uint8)
+    colours = np.where(rng.random((n_envs, max(n_words, 1))) < 0.5, palette[rng.integers(0, len(palette), (n_envs, max(n_words, 1)))],
+                       rng.integers(0, 256, (n_envs, max(n_words, 1)), dtype=np.uint8)).astype(np.uint8)
+    for e in range(n_envs):
+        scene = scenes[e // per]
+        G = len(scene.gems)
+        full = np.uint32((1 << G) - 1)
+        gems[e] &= full
+        if e % per == 0:
+            gems[e], beams[e] = 0, 0
+        elif e % per == 1:
+            gems[e], beams[e] = full, 0xFFFFFFFF
+        elif e % per == 2 and G:
+            gems[e] = np.uint32(1 << (G - 1))
+        if 2 <= e % per < 34:
+            beams[e] = np.uint32(1 << (e % per - 2))
+        elif 34 <= e % per < 40 and n_words:
+            beams[e] = 0
+            beams[e, rng.integers(0, n_words)] = np.uint32(1 << int(rng.integers(0, 32)))
+    tags = [cell_tags(s) for s in scenes]
+    by_tag = []
+    for t in tags:
+        d = {}
+        for c, ts in sorted(t.items()):
+            for name in ts - {"source"}:
+                d.setdefault(name, []).append(c)
+        by_tag.append(d)
+    for e in range(n_envs):
+        d = by_tag[e // per]
+        names = sorted(d)
+        for a in range(n_agents):
+            if a > 0 and (e % per == 3 or rng.random() < 0.25):
+                c = tuple(pos[e, rng.integers(0, a)])
+            else:
+                cells = d[names[rng.integers(0, len(names))]]
+                c = cells[rng.integers(0, len(cells))]
+            pos[e, a] = c
+    for e, a, c in planted:
+        pos[e, a] = c
+    return dict(pos=pos, gems=gems, beams=beams[:, :n_words], colours=colours[:, :n_words])
+
+
+def classes_hit(scenes, pos):
+    """The set of cell tags (cell_tags) that hold an agent somewhere in pos [n, A, 2]; no agent may stand on a laser source (the kernel
+    documents that a source's cell holds no agent, and the reference would hide one there)."""
+    tags = [cell_tags(s) for s in scenes]
+    per = len(pos) // len(scenes)
+    hit = set()
+    for e in range(len(pos)):
+        for p in pos[e]:
+            ts = tags[e // per][(int(p[0]), int(p[1]))]
+            assert "source" not in ts, "a source's cell holds no agent"
+            hit |= ts
+    return hit
+
+
+def write_states(bw, pos=None, gems=None, beams=None, colours=None):
+    """Write synthetic states straight into the device buffers the renderer reads (BatchedWorld.pos / .gems / .beams / .src_colour
+    are views of them).  No step may follow: the engine's invariants are not kept."""
+    import torch
+
+    def put(view, arr, as_type):
+        if arr is not None and view.numel():
+            view.copy_(torch.from_numpy(np.ascontiguousarray(arr).view(as_type).reshape(tuple(view.shape))).to(view.device))
+    put(bw.pos, pos, np.uint8)
+    put(bw.gems, gems, np.int32)
+    put(bw.beams, beams, np.int32)
+    put(bw.src_colour, colours, np.uint8)
+    torch.cuda.synchronize(bw.device)
+
+
+def check_frames(bw, atlas, env_ids=None, env_sources=False, where="", dtype=None, cells=None, frames=None):
+    """bw.render(env_ids, atlas, dtype) == the restatement of every selected env's current state, byte for byte.  atlas: a
+    SpriteAtlas (None: the built-in one).  cells: compare only the tiles of these (i, j) -- with their grid lines --, cropped on the
+    device before the copy.  frames: a tensor rendered by the caller (instead of bw.render).  An id outside the batch: zeros."""
+    import torch
+
+    from lle_amd.rendering import SpriteAtlas
+    dtype = torch.uint8 if dtype is None else dtype
+    got = bw.render(env_ids=env_ids, atlas=atlas, dtype=dtype) if frames is None else frames
+    assert got.dtype == dtype
+    T = TILE_SIZE
+    boxes = None if cells is None else [(T * i, T * (i + 1) + 1, T * j, T * (j + 1) + 1) for i, j in cells]
+
+    def to_host(t):  # (0 .. 255 are exact in every dtype; numpy has no bfloat16)
+        t = t.contiguous().cpu()
+        return (t if t.dtype == torch.uint8 else t.float()).numpy()
+    host = [to_host(got)] if boxes is None else [to_host(got[:, y0:y1, x0:x1]) for y0, y1, x0, x1 in boxes]
+    states = states_of(bw, env_sources)
+    scenes = [Scene.of(m) for m in bw.maps]
+    atlas = SpriteAtlas.builtin() if atlas is None else atlas
+    ids = list(range(bw.n_envs)) if env_ids is None else [int(e) for e in env_ids]
+    assert got.shape[0] == len(ids)
+    for s, e in enumerate(ids):
+        if 0 <= e < bw.n_envs:
+            want = render(scenes[e // bw.envs_per_map], states[e], atlas)
+        else:
+            want = np.zeros((T * bw.map.height + 1, T * bw.map.width + 1, 3), np.uint8)
+        parts = [want] if boxes is None else [want[y0:y1, x0:x1] for y0, y1, x0, x1 in boxes]
+        for k, (g, w) in enumerate(zip(host, parts)):
+            if not np.array_equal(g[s], w):
+                bad = np.argwhere((g[s] != w).any(axis=2))
+                oy, ox = (0, 0) if boxes is None else (boxes[k][0], boxes[k][2])
+                raise AssertionError(f"{where} env {e} ({dtype}): {len(bad)} pixels differ, first (y, x) {[int(bad[0][0]) + oy, int(bad[0][1]) + ox]}: "
+                                     f"got {g[s][tuple(bad[0])].tolist()}, want {w[tuple(bad[0])].tolist()}")

@@ -1,6 +1,7 @@
 """Rendering without a GPU: frame shapes, the PNG reader, rotations, the blend arithmetic of the restatement (tests/render_ref.py),
-the built-in sprites, lle_map_cell_layers, the exports of liblle_render.so, the refusal without a device and the ISA tripwire on the
-render kernel's translation unit.  The frames themselves are compared on the MI355X (tests/test_gpu_render.py)."""
+the restatement against two frames the reference's own renderer drew (tests/golden/reference_frames), the built-in sprites,
+lle_map_cell_layers, the exports of liblle_render.so, the refusal without a device and the ISA tripwire on the render kernel's
+translation unit.  The kernel's frames are compared on the MI355X (tests/test_gpu_render.py, tests/test_gpu_render_states.py)."""
 import glob
 import importlib.util
 import os
@@ -9,7 +10,7 @@ import numpy as np
 import pytest
 
 from lle_amd import World, rendering
-from lle_amd._capi import Map
+from lle_amd._capi import LLE_POS_START, Map
 from tests import render_ref
 from tests.parity_util import EXTRA_MAPS, LONG_MAPS
 
@@ -109,6 +110,45 @@ def test_blend_hand_computed():
     for bg, fg, a, want in cases:
         got = render_ref.blend(np.array([[bg, bg, bg]], np.uint8), np.array([[fg, fg, fg, a]], np.uint8))
         assert got.tolist() == [[want] * 3], (bg, fg, a)
+
+
+# Frames the reference's own renderer drew (tests/golden/README.md): its docs/3x1.png and docs/example_custom.png, the map text of
+# the second from the module docstring of python/lle/__init__.py:126-132.  EXCLUDED: the cells whose sprites (agents, lasers, laser
+# sources) were redrawn after the pictures were made -- a constant, never computed from where mismatches fall.
+REFERENCE_FRAMES = {
+    "3x1": ("S0 G X", [(0, 0)]),
+    "example_custom": ("S0 . G . X\nS1 @ . . .\nL0E . . V V\n@  @ . V V\nG  . . . X", [(0, 0), (1, 0), (2, 0), (2, 1), (2, 2), (2, 3), (2, 4)]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(REFERENCE_FRAMES))
+def test_restatement_against_reference_frames(name):
+    """render_ref.render of the reset state with the reference's sprites == the frame the reference shipped, red and blue swapped
+    back: every grid pixel and every cell outside EXCLUDED byte for byte (floors, walls, exits, gems and voids blended over the
+    floor -- real blends, truncation included).  A failure is a finding about tests/render_ref.py.  The excluded cells must differ:
+    when they stop doing so the fixtures have been refreshed and the list can shrink."""
+    text, excluded = REFERENCE_FRAMES[name]
+    png = rendering.read_png(os.path.join(ROOT, "tests", "golden", "reference_frames", name + ".png"))
+    assert (png[..., 3] == 255).all()
+    ref = png[..., [2, 1, 0]]  # the files were written by a tool that expects BGR
+    m = Map(text)
+    scene = render_ref.Scene.of(m)
+    beams = [m.reset_beam(s.laser_id, s.agent_id) & 0xFFFFFFFF for s in m.sources()]  # (beams of at most 32 cells: one word each)
+    state = render_ref.State(m.positions(LLE_POS_START), 0, beams, None)
+    want = render_ref.render(scene, state, rendering.SpriteAtlas.from_directory(SPRITES))
+    assert ref.shape == want.shape == (32 * m.height + 1, 32 * m.width + 1, 3)
+    T = render_ref.TILE_SIZE
+    assert np.array_equal(ref[::T], want[::T]) and np.array_equal(ref[:, ::T], want[:, ::T]), "grid lines"
+    assert (want[::T] == render_ref.GRID_GREY).all() and (want[:, ::T] == render_ref.GRID_GREY).all()
+    assert set(excluded) <= {(i, j) for i in range(m.height) for j in range(m.width)}
+    for i in range(m.height):
+        for j in range(m.width):
+            a, b = ref[T * i + 1:T * (i + 1), T * j + 1:T * (j + 1)], want[T * i + 1:T * (i + 1), T * j + 1:T * (j + 1)]
+            if (i, j) in excluded:
+                assert not np.array_equal(a, b), f"cell {(i, j)} equals the reference's frame now: take it off the list"
+            else:
+                assert np.array_equal(a, b), f"cell {(i, j)}: {int((a != b).any(axis=2).sum())} pixels differ from the reference's frame"
+    assert len(excluded) == {"3x1": 1, "example_custom": 7}[name]
 
 
 def test_builtin_atlas_well_formed():
