@@ -17,7 +17,8 @@ def __getattr__(name):
     if name == "BatchedWorld":
         from .batched import BatchedWorld
         return BatchedWorld
-    if name in ("BatchedLLE", "Builder", "DeathStrategy", "level", "from_str", "from_file"):  # (lle.level(6).obs_type(...).build())
+    if name in ("BatchedLLE", "Builder", "DeathStrategy", "level", "from_str", "from_file", "SingleObjective", "MultiObjective", "PotentialShapedLLE",
+                "NoExtras", "LaserSubgoal", "MultiGenerator"):  # (lle.level(6).obs_type(...).build())
         from . import env
         return getattr(env, name)
     if name in ("Layered", "LayeredPadded", "ObservationType", "StateGenerator", "FlattenedLayered", "PartialGenerator",
@@ -28,5 +29,5 @@ def __getattr__(name):
 
 
 __all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorld", "Direction", "EventType", "FlattenedLayered", "Gem", "InvalidActionError", "InvalidLevelError",
-           "InvalidWorldStateError", "Laser", "LaserSource", "Layered", "LayeredPadded", "Map", "MapParseError",
-           "ObservationType", "ParsingError", "PartialGenerator", "StateGenerator", "World", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "types", "world"]
+           "InvalidWorldStateError", "Laser", "LaserSource", "LaserSubgoal", "Layered", "LayeredPadded", "Map", "MapParseError", "MultiGenerator", "MultiObjective", "NoExtras",
+           "ObservationType", "ParsingError", "PartialGenerator", "PotentialShapedLLE", "SingleObjective", "StateGenerator", "World", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "types", "world"]

@@ -4,8 +4,9 @@ The reference's `LLE` (python/lle/env/env.py:39-255) is a thin host class around
 strategy, `compute_done`, observation / state generators, `available_actions` (optionally without moves into foreign
 lasers), `randomize_lasers` on reset.  Every one of those pieces already runs on the GPU behind the C ABI
 (include/lle_hip.h); this class strings them together with the reference's argument names and meanings and returns
-device tensors with a leading env axis.  No marlenv dependency, no extras generators and no PBRS shaping (SURVEY.md
-section 9) -- the hot path and its immediate callers only; "rgb-image" frames come from the render kernel (lle_amd.rendering).
+device tensors with a leading env axis.  No marlenv dependency; "rgb-image" frames come from the render kernel
+(lle_amd.rendering); potential-based reward shaping and the laser-subgoal extras (`reward_strategy=`, `extras_generator=`) come
+from the shaping kernel (lle_amd.shaping, loaded only when one of them is asked for).
 
     env = BatchedLLE(Map(level=6), 65536, obs_type="layered", randomize_lasers=True)
     obs, state = env.reset()
@@ -17,7 +18,7 @@ from enum import IntEnum
 import torch
 
 from . import _capi
-from .batched import BatchedWorld
+from .batched import BatchedWorld, _current_stream_handle
 
 
 class DeathStrategy(IntEnum):
@@ -44,15 +45,156 @@ _OBS_KINDS = {
 _RGB_IMAGE = -1  # the kind of "rgb-image": frames of the render kernel (BatchedWorld.render), not an lle_batch_observe_as kind
 
 
+# ------------------------------------------------------------------ reward strategies and extras generators (descriptors)
+# The reference's classes (python/lle/env/reward_strategy.py, extras_generators.py) hold a World and per-episode numpy state.  Here
+# they only DESCRIBE what BatchedLLE computes on the device: same names, same argument order, `world` optional (None = the maps
+# of the environment they are handed to).
+class SingleObjective:
+    """reward_strategy.py:51-75: one scalar reward."""
+    objectives = ("reward",)
+
+    def __init__(self, n_agents=None):
+        self.n_agents = n_agents
+
+
+class MultiObjective:
+    """reward_strategy.py:78-109: [gem, exit, death, done]."""
+    objectives = ("gem", "exit", "death", "done")
+
+    def __init__(self, n_agents=None):
+        self.n_agents = n_agents
+
+
+def _as_map(world):
+    """Anything BatchedLLE accepts as ONE map (a Map, a map text), or a lle_amd.World."""
+    if isinstance(world, _capi.Map):
+        return world
+    if isinstance(getattr(world, "_map", None), _capi.Map):
+        return world._map
+    if isinstance(world, (list, tuple)):
+        return _as_map(world[0])
+    return _capi.Map(world)
+
+
+def _source_at(map_, position):
+    """World.source_at (lle_amd/world.py): the laser_id of the source at `position`."""
+    position = tuple(position)
+    if len(position) != 2 or position[0] < 0 or position[1] < 0 or position[0] >= map_.height or position[1] >= map_.width:
+        raise IndexError("Position out of bounds")
+    for s in map_.sources():
+        if (int(s.i), int(s.j)) == (int(position[0]), int(position[1])):
+            return int(s.laser_id)
+    raise ValueError(f"Tile at position {position} is not a laser source")
+
+
+def _resolve_sources(map_, sources):
+    """laser_ids of `sources`: None = every source of the map; (i, j) positions or objects with `.laser_id` (builder.py:88-99)."""
+    n = map_.n_sources
+    if sources is None:
+        return list(range(n))
+    out = []
+    for source in sources:
+        if isinstance(source, (tuple, list)):
+            out.append(_source_at(map_, source))
+        elif hasattr(source, "laser_id"):
+            lid = int(source.laser_id)
+            if not 0 <= lid < n:
+                raise ValueError(f"Invalid laser source: laser_id {lid} on a map with {n} sources")
+            out.append(lid)
+        else:
+            raise ValueError(f"Invalid laser source: {source}")
+    return out
+
+
+class PotentialShapedLLE:
+    """reward_strategy.py:112-181: potential-based shaping around `strategy` (a SingleObjective or a MultiObjective): crossing the
+    beam of a source of `lasers_to_reward` -- (i, j) positions or objects with `.laser_id`; None: every source; a source listed
+    twice counts twice, the reference iterates a list -- for the first time in an episode is worth `reward_value`."""
+
+    def __init__(self, strategy, world=None, gamma=0.99, reward_value=0.5, lasers_to_reward=None):
+        if not isinstance(strategy, (SingleObjective, MultiObjective)):
+            raise ValueError(f"PotentialShapedLLE wraps a SingleObjective or a MultiObjective, got {strategy!r}")
+        self.strategy, self.world = strategy, world
+        self.gamma, self.reward_value = float(gamma), float(reward_value)
+        self.lasers_to_reward = None if lasers_to_reward is None else list(lasers_to_reward)
+        if world is not None:
+            self.laser_ids(None)  # a position that is not a source raises here, like the reference's constructor
+
+    @property
+    def objectives(self):
+        return self.strategy.objectives + (("PBRS",) if isinstance(self.strategy, MultiObjective) else ())
+
+    def laser_ids(self, default_map):
+        return _resolve_sources(_as_map(self.world) if self.world is not None else default_map, self.lasers_to_reward)
+
+
+class NoExtras:
+    """extras_generators.py:36-43."""
+    size, meanings = 0, ()
+
+    def __init__(self, n_agents=None):
+        self.n_agents = n_agents
+
+    def columns(self, default_map):
+        return []
+
+
+class LaserSubgoal:
+    """extras_generators.py:75-101: per agent and source of `sources` (None: every source of the world), 1.0 once the agent has
+    stood on a tile of that source's beam in this episode."""
+
+    def __init__(self, world=None, sources=None):
+        self.world = world
+        self.sources = None if sources is None else list(sources)
+        if world is not None:
+            self.columns(None)
+
+    def columns(self, default_map):
+        """[(laser_id, meaning)] of the generator's columns."""
+        m = _as_map(self.world) if self.world is not None else default_map
+        srcs = m.sources()
+        return [(l, f"Source {l} at {(int(srcs[l].i), int(srcs[l].j))}") for l in _resolve_sources(m, self.sources)]
+
+
+def _as_generator(extra):
+    if isinstance(extra, (NoExtras, LaserSubgoal, MultiGenerator)):
+        return extra
+    if isinstance(extra, str) and extra == "laser_subgoal":  # builder.py:138-139
+        return LaserSubgoal()
+    raise ValueError(f"Invalid extra type: {extra}")  # builder.py:140-141
+
+
+class MultiGenerator:
+    """extras_generators.py:46-71: the columns of `generators` side by side."""
+
+    def __init__(self, *generators):
+        self.generators = [_as_generator(g) for g in generators]
+
+    def add(self, *generators):
+        self.generators.extend(_as_generator(g) for g in generators)
+
+    def columns(self, default_map):
+        return [c for g in self.generators for c in g.columns(default_map)]
+
+
 class BatchedLLE:
     """Arguments follow `LLE.__init__` / `Builder` (python/lle/env/env.py:72-114, builder.py:30-116):
     obs_type / state_type: ObservationType values ("layered", "flattened", "partial3x3", ..., "state", "normalized-state",
     "perspective", "layered-padded[-k]"; padding_size for plain "layered-padded"); obs_dtype (the layered-style observations in float32 -- the reference's --,
     float16 or bfloat16 instead of int8, straight from the kernels); walkable_lasers; randomize_lasers;
-    multi_objective (MultiObjective instead of SingleObjective); death_strategy "end" only, like the reference."""
+    multi_objective (MultiObjective instead of SingleObjective); death_strategy "end" only, like the reference.
+    reward_strategy / extras_generator (env.py:69-80): SingleObjective() / MultiObjective() / PotentialShapedLLE(...) and NoExtras() /
+    LaserSubgoal(...) / MultiGenerator(...) / "laser_subgoal" -- the descriptors above.  With a PotentialShapedLLE the reward is
+    float32 [n, 1] (shaped) or [n, 5] (MultiObjective underneath, the shaped term last; the reference's np.concat returns float64
+    there, here the tensor stays float32); with an extras generator -- any, also one without columns: E = 0 -- step() returns an
+    "extras" key, float32 [n, A, E].  Both come
+    from ONE launch of the shaping kernel behind the step launch (lle_amd.shaping).  An environment whose step was refused
+    (err != 0) keeps its positions and gets the shaped term of unchanged reached flags, gamma * potential - potential.  Without
+    the two arguments nothing changes: the shaping library is not even loaded."""
 
     def __init__(self, maps, n_envs, obs_type="layered", state_type="state", walkable_lasers=True, randomize_lasers=False,
-                 multi_objective=False, death_strategy="end", padding_size=0, device=None, seed=0, name=None, incremental_obs=False, obs_dtype=None):
+                 multi_objective=False, death_strategy="end", padding_size=0, device=None, seed=0, name=None, incremental_obs=False, obs_dtype=None,
+                 reward_strategy=None, extras_generator=None):
         if death_strategy == "respawn":
             raise NotImplementedError("Respawn strategy is not implemented yet")  # env.py:106-107
         if death_strategy != "end":
@@ -87,6 +229,27 @@ class BatchedLLE:
                             raise ValueError(f"randomize_lasers: laser source {s.laser_id} at {(s.i, s.j)} cannot be changed to agent ID "
                                              f"{c} since it would cross the start position of another agent")
         self.multi_objective = bool(multi_objective)
+        self.reward_strategy, self.extras_generator = reward_strategy, extras_generator
+        self._shaping = None
+        self._pbrs = reward_strategy if isinstance(reward_strategy, PotentialShapedLLE) else None
+        if reward_strategy is not None:
+            base = self._pbrs.strategy if self._pbrs is not None else reward_strategy
+            if not isinstance(base, (SingleObjective, MultiObjective)):
+                raise ValueError(f"Invalid reward strategy: {reward_strategy!r}")
+            if self.multi_objective and not isinstance(base, MultiObjective):
+                raise ValueError("multi_objective=True contradicts a reward_strategy over SingleObjective")
+            self.multi_objective = isinstance(base, MultiObjective)
+        self._extras_cols, self._extras_meanings = [], []
+        if extras_generator is not None:
+            cols = _as_generator(extras_generator).columns(self.world.map)
+            self._extras_cols, self._extras_meanings = [c[0] for c in cols], [c[1] for c in cols]
+        if self._pbrs is not None or self._extras_cols:
+            from . import shaping
+            self._ops = shaping
+            self._shaping = shaping.Shaping(self.world, self._pbrs.laser_ids(self.world.map) if self._pbrs is not None else [], self._extras_cols,
+                                            self._pbrs.gamma if self._pbrs is not None else 0.0, self._pbrs.reward_value if self._pbrs is not None else 0.0)
+            self._last_reward = None
+            self._shaping_reset(None)  # the batch is created reset (World::new calls reset)
         # incremental_obs: steps write only the lines of the layered rows that dynamic state can change (LLE_STEP_INCREMENTAL_OBS: the
         # others keep their bytes from the last full write) -- same observation, a third fewer bytes on level 6; the caller must not write
         # into `world.obs` itself
@@ -143,6 +306,90 @@ class BatchedLLE:
     @property
     def name(self):
         return self._name if self._name is not None else "LLE"  # (marlenv's default is the class name, env.py:116-120)
+
+    # ------------------------------------------------------------------ reward shaping and extras (lle_amd.shaping)
+    @property
+    def objectives(self):
+        """RewardStrategy.objectives (reward_strategy.py:31,56,88,141): ends in "PBRS" with shaping over MultiObjective."""
+        if self._pbrs is not None:
+            return list(self._pbrs.objectives)
+        return list((MultiObjective if self.multi_objective else SingleObjective).objectives)
+
+    @property
+    def extras_shape(self):
+        """(E,): env.py:98."""
+        return (len(self._extras_cols),)
+
+    @property
+    def extras_meanings(self):
+        """env.py:99: `Source {laser_id} at {pos}` per column, the positions those of map 0."""
+        return list(self._extras_meanings)
+
+    @property
+    def _shaped(self):
+        return self._pbrs is not None  # (with nothing to reward -- no source, an empty list -- the kernel writes the shaped term 0)
+
+    def _no_extras(self):
+        """The extras of a generator without columns (NoExtras, LaserSubgoal on a map without sources): float32 [n, A, 0]."""
+        return torch.zeros((self.n_envs, self.n_agents, 0), dtype=torch.float32, device=self.world.device)
+
+    def _reward_width(self):
+        return (5 if self._pbrs is not None else 4) if self.multi_objective else 1
+
+    def _shaping_reset(self, env_mask):
+        """RewardStrategy.reset + ExtraGenerator.reset followed by the first compute_potential / compute (env.py:194-196,203): both
+        arrays cleared and marked at the start cells, for the envs with env_mask != 0.  Runs AHEAD of the world's reset: the mask may
+        be the world's own `done`, which that reset rewrites."""
+        sh, ops = self._shaping, self._ops
+        if env_mask is not None:
+            env_mask = env_mask.to(self.world.device, torch.uint8).contiguous()
+        both = ops.LLE_SHAPING_CLEAR | ops.LLE_SHAPING_MARK_STARTS
+        sh.update(sh.make_args(strategy_ops=both, extras_ops=both, env_mask=env_mask), self.world._stream())
+
+    def _shaping_args(self, base, honour):
+        """(args, reward, extras) of the step's shaping launch over `base` (the wrapped strategy's reward): fresh output tensors."""
+        sh, ops, n, dev = self._shaping, self._ops, self.n_envs, self.world.device
+        shaped = self._shaped
+        reward = torch.empty((n, self._reward_width()), dtype=torch.float32, device=dev) if shaped else base
+        extras = torch.empty((n, self.n_agents, len(self._extras_cols)), dtype=torch.float32, device=dev) if self._extras_cols else None
+        args = sh.make_args(strategy_ops=ops.LLE_SHAPING_MARK_POS, extras_ops=ops.LLE_SHAPING_MARK_POS,
+                            flags=ops.LLE_SHAPING_HONOUR_AUTO_RESET if honour else 0, reward_kind=int(self.multi_objective),
+                            base_reward=base if shaped else None, reward_out=reward if shaped else None, extras_out=extras)
+        return args, reward, extras
+
+    def _shape(self, out, honour):
+        """The shaping launch behind a step: `out["reward"]` becomes the shaped reward, `out["extras"]` the extras."""
+        args, reward, extras = self._shaping_args(out["reward"], honour)
+        self._shaping.update(args, self.world._stream())
+        out["reward"] = self._last_reward = reward
+        if self.extras_generator is not None:
+            out["extras"] = extras if extras is not None else self._no_extras()
+        return out
+
+    def _finish(self, out, honour):
+        """What step() returns: `out` as it always was without the two arguments; with them the shaped reward and the "extras" key --
+        the key whenever a generator was given, [n, A, 0] where it has no column."""
+        if self._shaping is not None:
+            return self._shape(out, honour)
+        if self.extras_generator is not None:
+            out["extras"] = self._no_extras()
+        return out
+
+    def extras(self):
+        """ExtraGenerator.compute (extras_generators.py:93-98; Observation.extras of get_observation, env.py:218-223) for every env:
+        float32 [n, A, E] -- the agents are marked at their current positions first.  E = 0 without a generator."""
+        n, dev = self.n_envs, self.world.device
+        if not self._extras_cols:
+            return self._no_extras()
+        out = torch.empty((n, self.n_agents, len(self._extras_cols)), dtype=torch.float32, device=dev)
+        sh = self._shaping
+        sh.update(sh.make_args(extras_ops=self._ops.LLE_SHAPING_MARK_POS, extras_out=out), self.world._stream())
+        return out
+
+    def __del__(self):
+        sh = getattr(self, "_shaping", None)
+        if sh is not None:
+            sh.free()
 
     # ------------------------------------------------------------------ static description (env.py:72-143)
     @property
@@ -225,6 +472,8 @@ class BatchedLLE:
         """world.reset() and, with randomize_lasers, the recolouring of the same envs: one launch either way
         (lle_batch_reset or lle_batch_reset_sources)."""
         w = self.world
+        if self._shaping is not None:
+            self._shaping_reset(env_mask)
         if self.randomize_lasers or colours is not None:
             if colours is None:
                 colours = torch.randint(0, self.n_agents, (self.n_envs, w.map.n_sources), generator=self._gen,
@@ -241,6 +490,14 @@ class BatchedLLE:
         w = self.world
         if agents_alive is None:
             agents_alive = torch.ones((self.n_envs, self.n_agents), dtype=torch.bool, device=w.device)
+        if self._shaping is not None and self._shaped:
+            # reward_strategy.reset() -- cleared, marked where the agents stand BEFORE the call -- then compute_reward(events) marks
+            # them where they stand after it (env.py:213-215); the extras generator is not touched until it computes next
+            sh, ops = self._shaping, self._ops
+            sh.update(sh.make_args(strategy_ops=ops.LLE_SHAPING_CLEAR | ops.LLE_SHAPING_MARK_POS), w._stream())
+            w.set_state(positions, gems_collected, agents_alive)
+            sh.update(sh.make_args(strategy_ops=ops.LLE_SHAPING_MARK_POS), w._stream())
+            return w.err
         w.set_state(positions, gems_collected, agents_alive)
         return w.err
 
@@ -317,6 +574,10 @@ class BatchedLLE:
     def reward(self):
         """Reward of the last step: SingleObjective float32 [n, 1] or MultiObjective float32 [n, 4]
         (reward_strategy.py:58-75, 90-109)."""
+        if self._pbrs is not None:  # (the shaped term is a function of the reached flags BEFORE the step: kept from the step itself)
+            if self._last_reward is None:
+                raise RuntimeError("reward() under PotentialShapedLLE returns the reward of the last step(): there has been none")
+            return self._last_reward
         reward = torch.empty((self.n_envs, 4 if self.multi_objective else 1), dtype=torch.float32, device=self.world.device)
         self.world.env_outputs(reward=reward, multi_objective=self.multi_objective)
         return reward
@@ -378,6 +639,9 @@ class BatchedLLE:
             if self.walkable_lasers:
                 fresh = self._fresh_outputs()
         env_out = fresh[1] if fresh is not None else (self._fused_outputs()[1] if fused else None)
+        # envs the step kernel resets itself are recognised by the shaping launch (LLE_BUF_EVCOUNT bit 7); a host-side reset
+        # (_reset_world) resets the shaping state itself
+        honour = bool(auto_reset) and (self._recolour_in_step or not self.randomize_lasers)
         if auto_reset:
             if self._recolour_in_step:
                 # world.reset() + a fresh colour per source for the envs that are over, inside the step kernel; the draws
@@ -402,9 +666,10 @@ class BatchedLLE:
                     state = state.flatten(1)
             else:
                 obs, state = self._obs_and_state(t["state"])
-            return {"obs": obs, "state": state, "reward": t["reward"],
-                    "done": self.done, "available_actions": t["available"].view(torch.bool), "err": w.err}
-        return self._outputs()
+            out = {"obs": obs, "state": state, "reward": t["reward"],
+                   "done": self.done, "available_actions": t["available"].view(torch.bool), "err": w.err}
+            return self._finish(out, honour)
+        return self._finish(self._outputs(), honour)
 
     def _step_persistent(self, actions, auto_reset):
         """step(persistent=True): see step()."""
@@ -449,8 +714,21 @@ class BatchedLLE:
                 state = state[:, 0]
         if t["state"] is None and self.state_type == "flattened":
             state = state.flatten(1)
-        return {"obs": obs, "state": state, "reward": t["reward"], "done": self.done, "available_actions": t["available"].view(torch.bool),
-                "err": w.err}
+        out = {"obs": obs, "state": state, "reward": t["reward"], "done": self.done, "available_actions": t["available"].view(torch.bool),
+               "err": w.err}
+        if self._shaping is not None:
+            # the shaping call bound once, into persistent tensors that the next step overwrites
+            skey = ("shape", bool(auto_reset and (self._recolour_in_step or not self.randomize_lasers)))
+            if skey not in b:
+                b[skey] = self._shaping_args(t["reward"], skey[1])
+            args, reward, extras = b[skey]
+            self._shaping.update(args, _current_stream_handle(w.device))
+            out["reward"] = self._last_reward = reward
+            if self.extras_generator is not None:
+                out["extras"] = extras if extras is not None else self._no_extras()
+        elif self.extras_generator is not None:
+            out["extras"] = self._no_extras()
+        return out
 
     def _outputs(self):
         """obs / state / reward / done / available_actions / err after a step: one launch of lle_batch_env_outputs for
@@ -470,8 +748,8 @@ class BatchedLLE:
 
 class Builder:
     """`lle.level(6).obs_type("layered").randomize_lasers().build()` of the reference (python/lle/env/builder.py:12-166), for the
-    batch: the same chain, and `build(n_envs)` returns a BatchedLLE.  `pbrs` and `add_extras` belong to the parts of `LLE` that are
-    outside this package (reward shaping and extras generators) and say so."""
+    batch: the same chain, and `build(n_envs)` returns a BatchedLLE.  `pbrs` and `add_extras` still refuse: reward shaping and extras
+    enter as `build(n_envs, reward_strategy=PotentialShapedLLE(...), extras_generator=LaserSubgoal(...))`, the way LLE.__init__ takes them."""
 
     def __init__(self, map_or_text):
         self._map = map_or_text
@@ -513,18 +791,21 @@ class Builder:
         return self
 
     def pbrs(self, *args, **kwargs):
-        raise NotImplementedError("potential-based reward shaping is outside the scope of lle_amd (SURVEY.md section 2, row 9)")
+        raise NotImplementedError("Builder.pbrs is not implemented: pass reward_strategy=PotentialShapedLLE(SingleObjective(), gamma=..., reward_value=..., "
+                                  "lasers_to_reward=...) (and extras_generator=LaserSubgoal(...)) to build() or to BatchedLLE")
 
     def add_extras(self, *extras):
         if not extras:
             return self
-        raise NotImplementedError("extras generators are outside the scope of lle_amd (SURVEY.md section 2, row 9)")
+        raise NotImplementedError("Builder.add_extras is not implemented: pass extras_generator=LaserSubgoal(...) or \"laser_subgoal\" to build() or to BatchedLLE")
 
-    def build(self, n_envs=1, device=None, seed=0, obs_dtype=None):
-        """(n_envs, device, seed, obs_dtype: what a batch needs beyond the reference's builder -- BatchedLLE's arguments of the same names)"""
+    def build(self, n_envs=1, device=None, seed=0, obs_dtype=None, reward_strategy=None, extras_generator=None):
+        """(n_envs, device, seed, obs_dtype: what a batch needs beyond the reference's builder -- BatchedLLE's arguments of the same names;
+        reward_strategy, extras_generator: LLE.__init__'s, env.py:69-80)"""
         return BatchedLLE(self._map, n_envs, obs_type=self._obs_type, state_type=self._state_type, walkable_lasers=self._walkable_lasers,
                           randomize_lasers=self._randomize_lasers, multi_objective=self._multi_objective, death_strategy=self._death_strategy,
-                          padding_size=self._padding_size, device=device, seed=seed, name=self._env_name, obs_dtype=obs_dtype)
+                          padding_size=self._padding_size, device=device, seed=seed, name=self._env_name, obs_dtype=obs_dtype,
+                          reward_strategy=reward_strategy, extras_generator=extras_generator)
 
 
 def level(level):
