@@ -117,6 +117,7 @@ class Shaping:
         if not self.h:
             raise RuntimeError(f"lle_shaping_create failed: {L.lle_shaping_last_error().decode()}")
         self._update = L.lle_shaping_update
+        self._device, self._shape = batch.device, (int(batch.n_envs), int(batch.map.n_agents))
 
     def _check(self, rc):
         if rc != 0:
@@ -139,6 +140,19 @@ class Shaping:
 
     def reached_ptr(self, which):
         return lib().lle_shaping_reached(self.h, int(which))
+
+    def reached(self, which):
+        """The device array behind lle_shaping_reached as a torch tensor, int32 [n_envs, A] (the bits of the u32 words): a VIEW of the
+        handle's memory, not a copy -- writes land in the state the next update reads.  which: 0 reward strategy, 1 extras generator.
+        Valid until free()."""
+        import torch
+        ptr = self.reached_ptr(which)
+        if not ptr:
+            raise RuntimeError(f"lle_shaping_reached failed: {lib().lle_shaping_last_error().decode()}")
+
+        class _Words:  # (the array interface keeps no owner: the handle owns the memory)
+            __cuda_array_interface__ = {"shape": self._shape, "typestr": "<i4", "data": (int(ptr), False), "version": 2, "strides": None}
+        return torch.as_tensor(_Words(), device=self._device)
 
     def free(self):
         if getattr(self, "h", None):
