@@ -21,6 +21,9 @@ def __getattr__(name):
                 "NoExtras", "LaserSubgoal", "MultiGenerator"):  # (lle.level(6).obs_type(...).build())
         from . import env
         return getattr(env, name)
+    if name == "CooperationTracker":
+        from .cooperation import CooperationTracker
+        return CooperationTracker
     if name in ("Layered", "LayeredPadded", "ObservationType", "StateGenerator", "FlattenedLayered", "PartialGenerator",
                 "AgentZeroPerspective"):
         from . import observations
@@ -28,6 +31,6 @@ def __getattr__(name):
     raise AttributeError(name)
 
 
-__all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorld", "Direction", "EventType", "FlattenedLayered", "Gem", "InvalidActionError", "InvalidLevelError",
+__all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorld", "CooperationTracker", "Direction", "EventType", "FlattenedLayered", "Gem", "InvalidActionError", "InvalidLevelError",
            "InvalidWorldStateError", "Laser", "LaserSource", "LaserSubgoal", "Layered", "LayeredPadded", "Map", "MapParseError", "MultiGenerator", "MultiObjective", "NoExtras",
            "ObservationType", "ParsingError", "PartialGenerator", "PotentialShapedLLE", "SingleObjective", "StateGenerator", "World", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "types", "world"]

@@ -399,6 +399,8 @@ class BatchedWorld:
     def _refresh_renderers(self, map_index):
         for r in getattr(self, "_renderers", {}).values():
             r.update_map(map_index, self.maps[map_index], self._stream())
+        for t in list(getattr(self, "_coop_trackers", ())):  # (lle_amd.cooperation: colour masks, enabled mask and start edges follow)
+            t.update_map(map_index)
 
     def render_desc(self, n_sel=None, dtype=torch.uint8, atlas=None):
         """Shape / strides (elements) / bytes of render()'s output for n_sel environments (lle_render_desc)."""

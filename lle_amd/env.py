@@ -190,11 +190,16 @@ class BatchedLLE:
     "extras" key, float32 [n, A, E].  Both come
     from ONE launch of the shaping kernel behind the step launch (lle_amd.shaping).  An environment whose step was refused
     (err != 0) keeps its positions and gets the shaped term of unchanged reached flags, gamma * potential - potential.  Without
-    the two arguments nothing changes: the shaping library is not even loaded."""
+    the two arguments nothing changes: the shaping library is not even loaded.
+    cooperation=True: `env.cooperation` is a CooperationTracker (lle_amd.cooperation) -- the help edges of every environment's current
+    state, their OR over its running episode and over its last finished one, each with a degree profile -- kept by ONE launch of the coop
+    kernel behind every step (and behind the shaping launch where there is one), reset and set_state.  reset(mask) finishes and clears
+    the selected environments and marks their reset state; set_state continues the episode with the new state; a refused step
+    (err != 0) marks the unchanged state again, which only counts one more state.  Without the argument the library is not loaded."""
 
     def __init__(self, maps, n_envs, obs_type="layered", state_type="state", walkable_lasers=True, randomize_lasers=False,
                  multi_objective=False, death_strategy="end", padding_size=0, device=None, seed=0, name=None, incremental_obs=False, obs_dtype=None,
-                 reward_strategy=None, extras_generator=None):
+                 reward_strategy=None, extras_generator=None, cooperation=False):
         if death_strategy == "respawn":
             raise NotImplementedError("Respawn strategy is not implemented yet")  # env.py:106-107
         if death_strategy != "end":
@@ -269,6 +274,20 @@ class BatchedLLE:
                                and all(m.n_beam_words <= 8 for m in self.world.maps)
                                and self._state_kind[0] in (_capi.LLE_OBS_STATE, _capi.LLE_OBS_NORMALIZED_STATE, _capi.LLE_OBS_PARTIAL))
         self._bound = {}    # bound calls over persistent buffers (step(..., persistent=True)): BatchedWorld.bound_*
+        self.cooperation = None
+        if cooperation:
+            from . import cooperation as coop
+            self._coop_ops = coop
+            self.cooperation = coop.CooperationTracker(self.world)
+            if self.randomize_lasers and self._recolour_in_step:
+                # the start edges of a map with a start cell on a laser cell depend on the colours an auto-reset draws inside the step
+                # kernel (LLE_COOP_HONOUR_AUTO_RESET refuses): such an env is reset on the host ahead of the step, where the tracker
+                # sees the reset state itself
+                for m in self.world.maps:
+                    cells = coop.cell_masks(m)
+                    if any(cells[i * m.width + j] for i, j in m.positions(_capi.LLE_POS_START)):
+                        self._recolour_in_step = False
+            self.cooperation.update(coop.LLE_COOP_CLEAR | coop.LLE_COOP_MARK_POS)  # the batch is created reset (World::new calls reset)
 
     @staticmethod
     def _kind(name, padding_size):
@@ -370,10 +389,17 @@ class BatchedLLE:
         """What step() returns: `out` as it always was without the two arguments; with them the shaped reward and the "extras" key --
         the key whenever a generator was given, [n, A, 0] where it has no column."""
         if self._shaping is not None:
-            return self._shape(out, honour)
-        if self.extras_generator is not None:
+            out = self._shape(out, honour)
+        elif self.extras_generator is not None:
             out["extras"] = self._no_extras()
+        if self.cooperation is not None:
+            self._coop_step(honour)
         return out
+
+    def _coop_step(self, honour):
+        """The coop launch behind a step (and behind its shaping launch): the new state is one more state of every environment's
+        episode; an environment the step kernel reset first finishes its episode and starts the next at the map's start edges."""
+        self.cooperation.update(self._coop_ops.LLE_COOP_MARK_POS, honour_auto_reset=honour)
 
     def extras(self):
         """ExtraGenerator.compute (extras_generators.py:93-98; Observation.extras of get_observation, env.py:218-223) for every env:
@@ -390,6 +416,9 @@ class BatchedLLE:
         sh = getattr(self, "_shaping", None)
         if sh is not None:
             sh.free()
+        tracker = getattr(self, "cooperation", None)
+        if tracker is not None:
+            tracker.free()
 
     # ------------------------------------------------------------------ static description (env.py:72-143)
     @property
@@ -474,6 +503,8 @@ class BatchedLLE:
         w = self.world
         if self._shaping is not None:
             self._shaping_reset(env_mask)
+        if self.cooperation is not None and env_mask is not None:
+            env_mask = env_mask.to(w.device, torch.uint8).clone()  # (the mask may be the world's own `done`, which the reset rewrites)
         if self.randomize_lasers or colours is not None:
             if colours is None:
                 colours = torch.randint(0, self.n_agents, (self.n_envs, w.map.n_sources), generator=self._gen,
@@ -481,6 +512,8 @@ class BatchedLLE:
             w.set_sources(colours=colours, env_mask=env_mask, reset_first=True, write_obs=write_obs)
         else:
             w.reset(env_mask)
+        if self.cooperation is not None:
+            self.cooperation.reset(env_mask)  # FINISH | CLEAR, then MARK_POS on the reset state
 
     def set_state(self, positions, gems_collected, agents_alive=None):
         """LLE.set_state (env.py:208-217) for every env: World.set_state with the reference's semantics (lossy
@@ -497,8 +530,10 @@ class BatchedLLE:
             sh.update(sh.make_args(strategy_ops=ops.LLE_SHAPING_CLEAR | ops.LLE_SHAPING_MARK_POS), w._stream())
             w.set_state(positions, gems_collected, agents_alive)
             sh.update(sh.make_args(strategy_ops=ops.LLE_SHAPING_MARK_POS), w._stream())
-            return w.err
-        w.set_state(positions, gems_collected, agents_alive)
+        else:
+            w.set_state(positions, gems_collected, agents_alive)
+        if self.cooperation is not None:
+            self.cooperation.mark()  # the episode continues with the new state
         return w.err
 
     def agents_alive(self):
@@ -728,6 +763,8 @@ class BatchedLLE:
                 out["extras"] = extras if extras is not None else self._no_extras()
         elif self.extras_generator is not None:
             out["extras"] = self._no_extras()
+        if self.cooperation is not None:
+            self._coop_step(bool(auto_reset and (self._recolour_in_step or not self.randomize_lasers)))
         return out
 
     def _outputs(self):
@@ -799,13 +836,13 @@ class Builder:
             return self
         raise NotImplementedError("Builder.add_extras is not implemented: pass extras_generator=LaserSubgoal(...) or \"laser_subgoal\" to build() or to BatchedLLE")
 
-    def build(self, n_envs=1, device=None, seed=0, obs_dtype=None, reward_strategy=None, extras_generator=None):
-        """(n_envs, device, seed, obs_dtype: what a batch needs beyond the reference's builder -- BatchedLLE's arguments of the same names;
-        reward_strategy, extras_generator: LLE.__init__'s, env.py:69-80)"""
+    def build(self, n_envs=1, device=None, seed=0, obs_dtype=None, reward_strategy=None, extras_generator=None, cooperation=False):
+        """(n_envs, device, seed, obs_dtype, cooperation: what a batch needs beyond the reference's builder -- BatchedLLE's arguments of the
+        same names; reward_strategy, extras_generator: LLE.__init__'s, env.py:69-80)"""
         return BatchedLLE(self._map, n_envs, obs_type=self._obs_type, state_type=self._state_type, walkable_lasers=self._walkable_lasers,
                           randomize_lasers=self._randomize_lasers, multi_objective=self._multi_objective, death_strategy=self._death_strategy,
                           padding_size=self._padding_size, device=device, seed=seed, name=self._env_name, obs_dtype=obs_dtype,
-                          reward_strategy=reward_strategy, extras_generator=extras_generator)
+                          reward_strategy=reward_strategy, extras_generator=extras_generator, cooperation=cooperation)
 
 
 def level(level):
