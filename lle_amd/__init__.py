@@ -24,6 +24,12 @@ def __getattr__(name):
     if name == "CooperationTracker":
         from .cooperation import CooperationTracker
         return CooperationTracker
+    if name in ("Solver", "solve", "SolveMode", "SolverCapacityError"):  # (lle.solver: the exact shortest-plan search, liblle_search.so)
+        from . import solver
+        return getattr(solver, name)
+    if name == "WorldCharacterizer":
+        from .characterization import WorldCharacterizer
+        return WorldCharacterizer
     if name in ("Layered", "LayeredPadded", "ObservationType", "StateGenerator", "FlattenedLayered", "PartialGenerator",
                 "AgentZeroPerspective"):
         from . import observations
@@ -33,4 +39,4 @@ def __getattr__(name):
 
 __all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorld", "CooperationTracker", "Direction", "EventType", "FlattenedLayered", "Gem", "InvalidActionError", "InvalidLevelError",
            "InvalidWorldStateError", "Laser", "LaserSource", "LaserSubgoal", "Layered", "LayeredPadded", "Map", "MapParseError", "MultiGenerator", "MultiObjective", "NoExtras",
-           "ObservationType", "ParsingError", "PartialGenerator", "PotentialShapedLLE", "SingleObjective", "StateGenerator", "World", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "types", "world"]
+           "ObservationType", "ParsingError", "PartialGenerator", "PotentialShapedLLE", "SingleObjective", "SolveMode", "Solver", "SolverCapacityError", "StateGenerator", "World", "WorldCharacterizer", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "solve", "types", "world"]

@@ -8,8 +8,9 @@ call.  The graph queries are host Python over a few dozen edges, written from th
     which every temporal edge (helper, beneficiary, t) is used at most once; agents may be revisited;
   * a CLOSED trail of order k ends at the agent it starts from and visits exactly k distinct agents.
 
-`WorldCharacterizer`, `Solver` and the generator (the SAT side of lle.characterization) are out of scope.  For whole batches use
-`BatchedLLE(..., cooperation=True)`.
+`WorldCharacterizer` answers the solver-backed questions -- solvable within t_max, the shortest plan, is cooperation required -- with
+the exact shortest-plan search of lle_amd.solver (liblle_search.so) in place of the reference's SAT encoding; the predicates that
+need the other solve modes, and the generator, are out of scope.  For whole batches use `BatchedLLE(..., cooperation=True)`.
 """
 from dataclasses import dataclass
 from functools import lru_cache
@@ -214,4 +215,90 @@ def profile_plan(world, plan, reset=True):
     return TemporalCooperationGraph.from_plan(plan, world, reset=reset).profile()
 
 
-__all__ = ["profile_plan", "detect_dependencies", "DependencyEdge", "TemporalCooperationGraph", "PlanProfile"]
+class WorldCharacterizer:
+    """Lazy characterisation of a world at the horizon `t_max` (python/lle/characterization/world_characterization.py): every property
+    depends on t_max -- a world can require cooperation within 10 steps and have an independent detour of 11.  `world`: an
+    lle_amd.World, a Map or map text; `solver_options` (chunk, max_states, device) go to lle_amd.solver.Solver.  Results are cached."""
+
+    def __init__(self, world, t_max, **solver_options):
+        from .solver import Solver
+        self._solver = Solver(world, t_max, **solver_options)
+        self.world = self._solver.world
+        self.t_max = self._solver.t_max
+        self._results = {}
+
+    def _cached(self, key, compute):
+        if key not in self._results:
+            self._results[key] = compute()
+        return self._results[key]
+
+    @property
+    def n_laser_colours(self):
+        """Number of distinct agent colours that own a laser source."""
+        return self._cached("colours", lambda: len({source.agent_id for source in self.world.laser_sources}))
+
+    @property
+    def shortest_path(self):
+        """The shortest plan within t_max, or None."""
+        return self._cached("standard", lambda: self._solver.find_shortest("standard"))
+
+    @property
+    def shortest_independent_path(self):
+        """The shortest plan within t_max in which nobody stands on a beam tile of another colour, or None."""
+        return self._cached("no-cooperation", lambda: self._solver.find_shortest("no-cooperation"))
+
+    def is_solvable(self):
+        return self.shortest_path is not None
+
+    def is_cooperative(self):
+        if not self.is_solvable():
+            return False
+        return self.shortest_independent_path is None
+
+    def is_independent(self):
+        if not self.is_solvable():
+            return False
+        return self.shortest_independent_path is not None
+
+    @staticmethod
+    def _needs(mode):
+        raise NotImplementedError(f"this predicate needs the solve mode '{mode}', which the search does not build "
+                                  "(it serves 'standard' and 'no-cooperation')")
+
+    def is_asymmetric(self):
+        self._needs("no-asymmetric")
+
+    def is_fully_coupled(self):
+        self._needs("no-fully-coupled")
+
+    def is_sequential(self, length=2):
+        if length < 2:
+            raise ValueError(f"Sequence length must be >= 2, got {length}.")
+        self._needs(f"no-sequence-{length}")
+
+    def is_convergent(self, k=2):
+        if k < 2:
+            raise ValueError(f"Convergence requires at least 2 distinct helpers, got {k}.")
+        self._needs(f"no-convergence-{k}")
+
+    def is_divergent(self, k=2):
+        if k < 2:
+            raise ValueError(f"Divergence requires at least 2 distinct beneficiaries, got {k}.")
+        self._needs(f"no-divergence-{k}")
+
+    def is_interdependent(self, n_agents=2):
+        if n_agents < 2:
+            raise ValueError(f"Interdependence only makes sense for >= 2 agents. Got {n_agents}.")
+        self._needs(f"no-interdependence-{n_agents}")
+
+    def is_mutual(self):
+        self._needs("no-mutual")
+
+    def __eq__(self, other):
+        return isinstance(other, WorldCharacterizer) and self.world == other.world and self.t_max == other.t_max
+
+    def __hash__(self):
+        return hash((self.world, self.t_max))
+
+
+__all__ = ["profile_plan", "detect_dependencies", "DependencyEdge", "TemporalCooperationGraph", "PlanProfile", "WorldCharacterizer"]
