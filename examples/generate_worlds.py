@@ -1,0 +1,26 @@
+"""Eight small worlds that cannot be solved without cooperation, generated and filtered on one MI355X.
+
+`generate_n` draws seeded candidate layouts from `lle_amd.mapgen` in batches and keeps those a `Constraint` accepts.  A batch is
+filtered by one `Constraint.satisfied_by_many`: two forest runs (lle_amd/liblle_forest.so) that walk the search trees of all its
+candidates in the same launches -- any plan, and a plan in which nobody stands in somebody else's beam.
+"""
+from lle_amd import Constraint, Cooperative, Solvable, characterize_many, generate_n, mapgen, solve_many
+
+keep = Constraint(t_max=12, predicate=Cooperative(), min_solution_length=4)
+worlds = list(generate_n(8, keep, height=5, width=5, n_agents=2, n_lasers=2, n_gems=1, n_exits=2, wall_fraction=0.12, seed=0, batch=128, max_attempts=2048))
+print(f"{len(worlds)} cooperative 5x5 worlds whose shortest plan has at least 4 steps")
+
+plans = solve_many(worlds, 12)                       # one forest: the shortest plan of every world
+answers = characterize_many(worlds, 12)
+for k, (world, plan) in enumerate(zip(worlds, plans)):
+    print(f"--- world {k}: shortest plan {len(plan)} steps, cooperative {bool(answers.cooperative[k])}, independent {bool(answers.independent[k])}")
+    print(world.world_string.rstrip())
+    world.reset()                                    # the plan runs on the world it was found for
+    for joint in plan:
+        world.step(list(joint))
+    assert all(agent.has_arrived for agent in world.agents)
+
+# the same vocabulary composes: solvable without help, in at most 12 steps
+easy = Constraint(12, Solvable() & ~Cooperative())
+candidates = [mapgen.generate(5, 5, 2, 2, 1, n_exits=2, wall_fraction=0.12, n_voids=0, seed=s) for s in range(64)]
+print("of the first 64 candidates,", int(easy.satisfied_by_many(candidates).sum()), "can be solved without cooperation")

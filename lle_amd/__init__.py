@@ -27,6 +27,13 @@ def __getattr__(name):
     if name in ("Solver", "solve", "SolveMode", "SolverCapacityError"):  # (lle.solver: the exact shortest-plan search, liblle_search.so)
         from . import solver
         return getattr(solver, name)
+    if name in ("ForestSolver", "ForestResult", "solve_many", "characterize_many"):  # (the same search over many maps at once, liblle_forest.so)
+        from . import forest
+        return getattr(forest, name)
+    if name in ("Predicate", "Solvable", "Independent", "Cooperative", "Asymmetric", "Sequential", "Convergent", "Divergent", "Interdependent", "And", "Or",
+                "Not", "WorldRequirements", "Constraint", "WorldFilter", "generate_n"):  # (lle.generator: the filter vocabulary)
+        from . import generator
+        return getattr(generator, name)
     if name == "WorldCharacterizer":
         from .characterization import WorldCharacterizer
         return WorldCharacterizer
@@ -39,4 +46,5 @@ def __getattr__(name):
 
 __all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorld", "CooperationTracker", "Direction", "EventType", "FlattenedLayered", "Gem", "InvalidActionError", "InvalidLevelError",
            "InvalidWorldStateError", "Laser", "LaserSource", "LaserSubgoal", "Layered", "LayeredPadded", "Map", "MapParseError", "MultiGenerator", "MultiObjective", "NoExtras",
-           "ObservationType", "ParsingError", "PartialGenerator", "PotentialShapedLLE", "SingleObjective", "SolveMode", "Solver", "SolverCapacityError", "StateGenerator", "World", "WorldCharacterizer", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "solve", "types", "world"]
+           "ObservationType", "ParsingError", "PartialGenerator", "PotentialShapedLLE", "SingleObjective", "SolveMode", "Solver", "SolverCapacityError", "StateGenerator", "World", "WorldCharacterizer", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "solve", "types", "world",
+           "ForestSolver", "ForestResult", "solve_many", "characterize_many", "Constraint", "WorldFilter", "generate_n"]
