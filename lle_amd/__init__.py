@@ -27,6 +27,9 @@ def __getattr__(name):
     if name in ("Solver", "solve", "SolveMode", "SolverCapacityError"):  # (lle.solver: the exact shortest-plan search, liblle_search.so)
         from . import solver
         return getattr(solver, name)
+    if name in ("OptimalPolicy", "PolicyCapacityError"):  # (steps-to-go and expert actions of a whole batch, liblle_policy.so)
+        from . import policy
+        return getattr(policy, name)
     if name in ("ForestSolver", "ForestResult", "solve_many", "characterize_many"):  # (the same search over many maps at once, liblle_forest.so)
         from . import forest
         return getattr(forest, name)
@@ -47,4 +50,5 @@ def __getattr__(name):
 __all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorld", "CooperationTracker", "Direction", "EventType", "FlattenedLayered", "Gem", "InvalidActionError", "InvalidLevelError",
            "InvalidWorldStateError", "Laser", "LaserSource", "LaserSubgoal", "Layered", "LayeredPadded", "Map", "MapParseError", "MultiGenerator", "MultiObjective", "NoExtras",
            "ObservationType", "ParsingError", "PartialGenerator", "PotentialShapedLLE", "SingleObjective", "SolveMode", "Solver", "SolverCapacityError", "StateGenerator", "World", "WorldCharacterizer", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "solve", "types", "world",
-           "ForestSolver", "ForestResult", "solve_many", "characterize_many", "Constraint", "WorldFilter", "generate_n"]
+           "ForestSolver", "ForestResult", "solve_many", "characterize_many", "Constraint", "WorldFilter", "generate_n",
+           "OptimalPolicy", "PolicyCapacityError"]

@@ -274,11 +274,14 @@ class BatchedWorld:
         else:
             if actions is None:
                 raise ValueError("actions is required unless sample=True")
-            if actions.dtype != torch.uint8 or not actions.is_contiguous() or actions.device != self.device:
-                actions = actions.to(self.device, torch.uint8).contiguous()
-            if tuple(actions.shape) != (self.n_envs, self.map.n_agents):
-                raise ValueError(f"Invalid number of actions: given {tuple(actions.shape)}, expected {(self.n_envs, self.map.n_agents)}")
-            ap = actions.data_ptr()
+            if actions is self.actions:  # the batch's own action buffer, filled in place (OptimalPolicy.act): the kernel reads it where it is
+                ap = None
+            else:
+                if actions.dtype != torch.uint8 or not actions.is_contiguous() or actions.device != self.device:
+                    actions = actions.to(self.device, torch.uint8).contiguous()
+                if tuple(actions.shape) != (self.n_envs, self.map.n_agents):
+                    raise ValueError(f"Invalid number of actions: given {tuple(actions.shape)}, expected {(self.n_envs, self.map.n_agents)}")
+                ap = actions.data_ptr()
         if auto_reset:
             flags |= LLE_STEP_AUTO_RESET
         if recolour_resets:  # (LLE.reset with randomize_lasers inside the step: per-env sources, see LLE_STEP_RECOLOUR_RESETS)
