@@ -5,8 +5,10 @@
 // lle_batch_create_multi, in which map m owns the environments [m * E, (m + 1) * E).  Per map a segment of everything search.hip
 // keeps: `cap` pool records (structure of arrays inside the segment), parent (u32, local index) and action (u16) per state, a table
 // segment of a power of two >= max(2 cap, cap + E + 1) slots, eight u64 counters and the foreign-beam table (H * W bytes).  Record
-// layout, hash, probe step and record predicates are those of ../search/search_logic.hpp; a tag is TAG_BIT | the candidate's index
-// inside its map's block, so a table segment only ever names records of its own map and every map's search is exactly the single one.
+// layout, hash, probe step, record predicates and the record I/O (scatter_item, occupant_is, copy_record) are those of
+// ../search/search_logic.hpp, the host-side helpers of a C ABI call those of ../search/search_device.hpp; a tag is TAG_BIT | the
+// candidate's index inside its map's block, so a table segment only ever names records of its own map and every map's search is
+// exactly the single one.  What is this file's own: which lane serves which map, the descriptors, the per-map counters and fates.
 //
 // A level: the host reads all counters in one copy, decides each map's fate (forest_logic.hpp: advance), writes one descriptor per map
 // in one copy and launches max over the active maps of ceil(items_m / E) pieces.  A piece is four launches over all n_maps * E lanes:
@@ -28,25 +30,19 @@
 #include <vector>
 
 #include "../../include/lle_forest.h"
+#include "../search/search_device.hpp"
 #include "forest_logic.hpp"
 
 namespace lle {
 
 namespace sl = lle_search_logic;
+namespace sd = lle_search_device;
 namespace fl = lle_forest_logic;
 
 constexpr int FOREST_THREADS = 256;
 
 struct ForestParams {
-    // the batch (include/lle_hip.h buffer descriptors, read once)
-    uint8_t* pos;          // LLE_BUF_POS
-    uint64_t* bits;        // LLE_BUF_BITS
-    uint32_t* gems;        // LLE_BUF_GEMS
-    uint32_t* beams;       // LLE_BUF_BEAMS
-    uint8_t* avail;        // LLE_BUF_AVAIL
-    uint8_t* actions;      // LLE_BUF_ACTIONS
-    const uint8_t* err;    // LLE_BUF_ERR
-    int64_t pos_stride, pos_agent_stride, beam_stride, avail_stride, act_stride;  // elements
+    sl::BatchView b;       // the batch (include/lle_hip.h buffer descriptors, read once)
     // the handle: one segment per map of each
     uint32_t* pool;        // [n_maps][n_words][cap]
     uint32_t* parent;      // [n_maps][cap]
@@ -69,39 +65,8 @@ struct ForestParams {
     uint64_t piece;
 };
 
-// Word w of the record in environment k of the batch.
-struct EnvRecord {
-    const ForestParams& p;
-    int64_t k;
-    __device__ uint32_t operator()(int w) const {
-        const sl::RecordLayout& r = p.lay;
-        if (w < r.n_pos) {
-            uint32_t v = 0u;
-            for (int b = 0; b < 4; b++) {
-                const int byte = 4 * w + b;
-                if (byte < 2 * r.A) v |= (uint32_t)p.pos[k * p.pos_stride + (byte >> 1) * p.pos_agent_stride + (byte & 1)] << (8 * b);
-            }
-            return v;
-        }
-        if (w == r.w_bits) return (uint32_t)p.bits[k];
-        if (w == r.w_bits + 1) return (uint32_t)(p.bits[k] >> 32);
-        if (w < r.w_gems) return p.beams[k * p.beam_stride + (w - r.w_beams)];
-        if (w == r.w_gems) return p.gems[k];
-        uint32_t v = 0u;
-        for (int b = 0; b < 4; b++) {
-            const int a = 4 * (w - r.w_avail) + b;
-            if (a < r.A) v |= (uint32_t)p.avail[k * p.avail_stride + a] << (8 * b);
-        }
-        return v;
-    }
-};
-// Word w of local state s of map `map`.
-struct PoolRecord {
-    const ForestParams& p;
-    int64_t map;
-    uint32_t s;
-    __device__ uint32_t operator()(int w) const { return p.pool[fl::pool_index(map, p.lay.n_words, w, p.cap, s)]; }
-};
+// The pool segment of map `map`: word w of local state s at [w * cap + s] (forest_logic.hpp: pool_index).
+__device__ inline uint32_t* pool_segment(const ForestParams& p, int64_t map) { return p.pool + (uint64_t)map * (uint64_t)p.lay.n_words * p.cap; }
 
 __device__ inline int64_t lane_index() { return (int64_t)blockIdx.x * FOREST_THREADS + threadIdx.x; }
 
@@ -109,7 +74,7 @@ __device__ inline int64_t lane_index() { return (int64_t)blockIdx.x * FOREST_THR
 __global__ __launch_bounds__(FOREST_THREADS) void forest_roots(ForestParams p) {
     const int64_t m = lane_index();
     if (m >= p.n_maps) return;
-    const EnvRecord rec{p, fl::env_index(m, p.E, 0)};
+    const sl::EnvRecord rec{p.b, p.lay, fl::env_index(m, p.E, 0)};
     for (int w = 0; w < p.lay.n_words; w++) p.roots[m * p.lay.n_words + w] = rec(w);
 }
 
@@ -134,31 +99,11 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_expand(ForestParams p) 
         p.valid[k] = 0;
         return;
     }
-    const sl::RecordLayout& r = p.lay;
     const uint32_t s = p.desc[lw.map].first_state + (uint32_t)(lw.item / p.n_joint);  // < the frontier's end <= cap
-    const uint32_t code = (uint32_t)(lw.item % p.n_joint);
-    const PoolRecord rec{p, lw.map, s};
-    uint32_t av[2] = {rec(r.w_avail), r.n_av > 1 ? rec(r.w_avail + 1) : 0u};
-    auto avail = [&](int a) { return (av[a >> 2] >> (8 * (a & 3))) & 255u; };
-    const bool valid = sl::joint_available(code, r.A, avail);
+    // (an invalid item leaves environment k as it is: whatever the step makes of it, forest_insert drops the item)
+    const bool valid = sl::scatter_item(p.b, p.lay, sl::PoolRecord{pool_segment(p, lw.map), p.cap, s}, k, (uint32_t)(lw.item % p.n_joint));
     p.valid[k] = valid ? 1 : 0;
-    if (!valid) return;  // (environment k stays as it is: whatever the step makes of it, forest_insert drops the item)
-    for (int w = 0; w < r.n_pos; w++) {
-        const uint32_t v = rec(w);
-        for (int b = 0; b < 4; b++) {
-            const int byte = 4 * w + b;
-            if (byte < 2 * r.A) p.pos[k * p.pos_stride + (byte >> 1) * p.pos_agent_stride + (byte & 1)] = (uint8_t)(v >> (8 * b));
-        }
-    }
-    p.bits[k] = (uint64_t)rec(r.w_bits) | (uint64_t)rec(r.w_bits + 1) << 32;
-    for (int w = 0; w < r.Lw; w++) p.beams[k * p.beam_stride + w] = rec(r.w_beams + w);
-    p.gems[k] = rec(r.w_gems);
-    uint32_t digits = code;
-    for (int a = 0; a < r.A; a++) {
-        p.avail[k * p.avail_stride + a] = (uint8_t)avail(a);
-        p.actions[k * p.act_stride + a] = (uint8_t)(digits % 5u);
-        digits /= 5u;
-    }
+    if (!valid) return;
     atomicAdd(&p.counters[fl::counter_index(lw.map, fl::CNT_EXPANDED)], 1ull);
 }
 
@@ -172,40 +117,25 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_insert(ForestParams p) 
     const uint32_t local = (uint32_t)(k % p.E);
     unsigned long long* counters = p.counters + fl::counter_index(map, 0);
     if (counters[fl::CNT_OVERFLOW] != 0ull) return;  // (set by an earlier launch: this map's search has failed already)
-    if (p.err[k] != 0) {  // the step refused a joint action the mask allowed
+    if (p.b.err[k] != 0) {  // the step refused a joint action the mask allowed
         atomicAdd(&counters[fl::CNT_STEP_ERRORS], 1ull);
         return;
     }
     const sl::RecordLayout& r = p.lay;
-    const EnvRecord me{p, k};
+    const sl::EnvRecord me{p.b, r, k};
     if (sl::anybody_dead(me(r.w_bits), r.A)) return;
     if constexpr (NO_COOP) {
         const uint8_t* foreign = p.foreign + fl::foreign_base(map, p.H, p.W);
         for (int a = 0; a < r.A; a++) {
-            const uint8_t* q = p.pos + k * p.pos_stride + a * p.pos_agent_stride;
+            const uint8_t* q = p.b.pos + k * p.b.pos_stride + a * p.b.pos_agent_stride;
             const int i = q[0], j = q[1];
             if (i < p.H && j < p.W && sl::on_foreign_beam(foreign[i * p.W + j], a)) return;
         }
     }
     const uint64_t h = sl::hash_record(me, r.n_key);
-    auto load = [](uint32_t* slot) { return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    auto cas = [](uint32_t* slot, uint32_t expected, uint32_t desired) { return atomicCAS(slot, expected, desired); };
-    auto same_as = [&](uint32_t occupant) {
-        if (occupant & sl::TAG_BIT) {
-            const uint32_t other = occupant & ~sl::TAG_BIT;
-            if ((int64_t)other >= p.E) return false;  // (no such tag in a sound table)
-            const EnvRecord rec{p, fl::env_index(map, p.E, other)};
-            for (int w = 0; w < r.n_key; w++)
-                if (rec(w) != me(w)) return false;
-            return true;
-        }
-        if ((uint64_t)occupant >= p.cap) return false;
-        const PoolRecord rec{p, map, occupant};
-        for (int w = 0; w < r.n_key; w++)
-            if (rec(w) != me(w)) return false;
-        return true;
-    };
-    const int64_t slot = sl::table_insert(p.table + fl::table_base(map, p.slots), (uint32_t)(p.slots - 1), h, sl::TAG_BIT | local, load, cas, same_as);
+    const sl::Occupants who{p.b.key(), fl::env_index(map, p.E, 0), (uint32_t)p.E, pool_segment(p, map), p.cap, p.cap};
+    auto same_as = [&](uint32_t occupant) { return sl::occupant_is(who, r, occupant, me); };
+    const int64_t slot = sl::table_insert(p.table + fl::table_base(map, p.slots), (uint32_t)(p.slots - 1), h, sl::TAG_BIT | local, sd::SlotLoad{}, sd::SlotCas{}, same_as);
     if (slot >= 0) p.win_slot[k] = (uint32_t)slot;
     else if (slot == sl::INSERT_FULL) atomicMax(&counters[fl::CNT_OVERFLOW], 1ull);
 }
@@ -223,13 +153,13 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_commit(ForestParams p) 
         return;
     }
     const sl::RecordLayout& r = p.lay;
-    const EnvRecord me{p, k};
-    for (int w = 0; w < r.n_words; w++) p.pool[fl::pool_index(map, r.n_words, w, p.cap, idx)] = me(w);
+    const sl::EnvRecord me{p.b, r, k};
+    sl::copy_record(p.b, r, k, pool_segment(p, map), p.cap, idx);
     const uint64_t item = p.piece * (uint64_t)p.E + (uint64_t)(k % p.E);
     p.parent[fl::state_index(map, p.cap, idx)] = p.desc[map].first_state + (uint32_t)(item / p.n_joint);
     p.action[fl::state_index(map, p.cap, idx)] = (uint16_t)(item % p.n_joint);
     p.table[fl::table_base(map, p.slots) + slot] = (uint32_t)idx;
-    if (sl::all_arrived(me(r.w_bits), r.A) && (!p.collect_gems || sl::all_gems(me(r.w_gems), p.G))) atomicMin(&counters[fl::CNT_GOAL], idx);
+    if (sl::is_goal(me(r.w_bits), me(r.w_gems), r, p.collect_gems != 0u, p.G)) atomicMin(&counters[fl::CNT_GOAL], idx);
 }
 
 // One lane per map; desc[m]: active = solved, first_state = the goal state, items = the plan's length (<= plan_rows).
@@ -266,61 +196,19 @@ template __global__ void forest_insert<true>(ForestParams);
 using lle::ForestParams;
 namespace sl = lle_search_logic;
 namespace fl = lle_forest_logic;
+namespace sd = lle_search_device;
+using sd::DeviceGuard;
+using sd::fail;
+using sd::g_error;
 
 namespace {
 
-thread_local std::string g_error;
 std::atomic<uint32_t> g_launched{0};
 enum { K_ROOTS = 0, K_SEED, K_EXPAND, K_INSERT, K_INSERT_NO_COOP, K_COMMIT, K_PLANS, K_COUNT };
 const char* const KERNEL_NAMES[K_COUNT] = {"forest_roots", "forest_seed", "forest_expand", "forest_insert<false>", "forest_insert<true>", "forest_commit",
                                            "forest_plans"};
 
-int fail(int code, const std::string& why) {
-    g_error = why;
-    return code;
-}
-
-struct DeviceGuard {  // the handle's device current for the call, the caller's put back
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-size_t names_out(uint32_t bits, char* buf, size_t cap) {
-    std::string s;
-    for (int k = 0; k < K_COUNT; k++)
-        if ((bits >> k) & 1u) s += std::string(KERNEL_NAMES[k]) + "\n";
-    if (buf && cap > 0) {
-        const size_t n = std::min(cap - 1, s.size());
-        std::memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return s.size() + 1;
-}
-
-// foreign[cell] of one map (search_logic.hpp: foreign_bit), appended to `all`.
-bool append_foreign(const lle_map* map, int H, int W, std::vector<uint8_t>& all, std::string& err) {
-    std::vector<lle_source_info> src((size_t)std::max(0, lle_map_sources(map, nullptr, 0)));
-    lle_map_sources(map, src.data(), (int)src.size());
-    const size_t base = all.size();
-    all.resize(base + (size_t)H * W, 0);
-    std::vector<lle_laser_tile> tiles((size_t)std::max(0, lle_map_laser_tiles(map, nullptr, 0)));
-    lle_map_laser_tiles(map, tiles.data(), (int)tiles.size());
-    for (const auto& t : tiles) {
-        if (t.i < 0 || t.i >= H || t.j < 0 || t.j >= W || t.laser_id < 0 || t.laser_id >= (int)src.size()) {
-            err = "laser tile out of range";
-            return false;
-        }
-        all[base + (size_t)t.i * W + t.j] |= sl::foreign_bit(src[(size_t)t.laser_id].agent_id);
-    }
-    return true;
-}
+static_assert(LLE_SEARCH_MAX_AGENTS == sl::MAX_AGENTS, "include/lle_search.h and search_logic.hpp disagree");
 
 struct MapRun {  // one map in the last run
     fl::MapProgress progress{};
@@ -432,25 +320,18 @@ lle_forest* lle_forest_create(const lle_map* const* maps, int n_maps, const lle_
         return refuse(LLE_ERR_ARG, "max_states_per_map + envs_per_map must be below 2^31 (a table segment has at most 2^31 slots)");
     lle_map_info info{};
     if (lle_map_get_info(maps[0], &info) != LLE_OK) return refuse(LLE_ERR_ARG, "lle_map_get_info failed");
-    if (info.n_agents > LLE_SEARCH_MAX_AGENTS || info.n_agents < 1)
-        return refuse(LLE_ERR_UNSUPPORTED, "more than 6 agents: a state has 5^A joint actions, the search serves maps of at most 6 agents (these maps have " +
-                                               std::to_string(info.n_agents) + ")");
-    if (info.n_beam_words > sl::MAX_BEAM_WORDS || info.n_gems > 32) return refuse(LLE_ERR_UNSUPPORTED, "more beam words or gems than a state record holds");
+    if (!sd::record_limits_ok(
+            info, "more than 6 agents: a state has 5^A joint actions, the search serves maps of at most 6 agents (these maps have "))
+        return nullptr;
     // the shapes, judged by the step library itself without a device: its refusal is the one lle_batch_create_multi would give
     if (lle_batch_arena_bytes_multi(maps, n_maps, E) < 0) return refuse(LLE_ERR_ARG, std::string("lle_batch_create_multi: ") + lle_last_error());
     const int H = info.height, W = info.width;
     std::vector<uint8_t> foreign;
-    std::string err;
     for (int m = 0; m < n_maps; m++)
-        if (!append_foreign(maps[m], H, W, foreign, err)) return refuse(LLE_ERR_ARG, err + " (map " + std::to_string(m) + ")");
-    int n_devices = 0;
-    if (hipGetDeviceCount(&n_devices) != hipSuccess || n_devices <= 0) {
-        (void)hipGetLastError();
-        return refuse(LLE_ERR_NO_DEVICE, "no HIP device: the search runs on the GPU only (there is no CPU fallback)");
-    }
-    int device = opt ? opt->device : -1;
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-    if (device >= n_devices) return refuse(LLE_ERR_ARG, "no such HIP device");
+        if (!sd::build_foreign(maps[m], H, W, foreign)) return refuse(LLE_ERR_ARG, "laser tile out of range (map " + std::to_string(m) + ")");
+    int device = -1;
+    if (sd::choose_device(opt ? opt->device : -1, "no HIP device: the search runs on the GPU only (there is no CPU fallback)", &device) != LLE_OK)
+        return nullptr;
 
     auto* f = new lle_forest();
     f->device = device;
@@ -470,16 +351,10 @@ lle_forest* lle_forest_create(const lle_map* const* maps, int n_maps, const lle_
     };
     f->batch = lle_batch_create_multi(maps, n_maps, E, device, nullptr, 0, f->stream);
     if (!f->batch) return give_up(LLE_ERR_HIP, std::string("lle_batch_create_multi: ") + lle_last_error());
-    lle_buffer_desc pos{}, bits{}, gems{}, beams{}, avail{}, actions{}, errs{};
-    if (lle_batch_get_buffer(f->batch, LLE_BUF_POS, &pos) || lle_batch_get_buffer(f->batch, LLE_BUF_BITS, &bits) ||
-        lle_batch_get_buffer(f->batch, LLE_BUF_GEMS, &gems) || lle_batch_get_buffer(f->batch, LLE_BUF_BEAMS, &beams) ||
-        lle_batch_get_buffer(f->batch, LLE_BUF_AVAIL, &avail) || lle_batch_get_buffer(f->batch, LLE_BUF_ACTIONS, &actions) ||
-        lle_batch_get_buffer(f->batch, LLE_BUF_ERR, &errs))
-        return give_up(LLE_ERR_ARG, "lle_batch_get_buffer failed");
-    if (pos.elem_bytes != 1 || bits.elem_bytes != 8 || gems.elem_bytes != 4 || beams.elem_bytes != 4 || avail.elem_bytes != 1 || actions.elem_bytes != 1 ||
-        errs.elem_bytes != 1 || pos.stride[0] < 2 * info.n_agents || avail.stride[0] < info.n_agents || actions.stride[0] < info.n_agents ||
-        beams.stride[0] < info.n_beam_words || lle_batch_n_envs(f->batch) != (int64_t)n_maps * E)
-        return give_up(LLE_ERR_UNSUPPORTED, "the batch's buffers do not have the layout include/lle_hip.h describes");
+    if (sd::bind_batch(f->batch, info, (int64_t)n_maps * E, &f->p.b) != LLE_OK) {
+        lle_forest_free(f);
+        return nullptr;
+    }
     const sl::RecordLayout lay = sl::make_layout(info.n_agents, info.n_beam_words, false);
     const uint64_t slots = fl::table_slots((uint64_t)cap, (uint64_t)E);
     const size_t HW = (size_t)H * W, M = (size_t)n_maps, lanes = M * (size_t)E;
@@ -496,18 +371,6 @@ lle_forest* lle_forest_create(const lle_map* const* maps, int n_maps, const lle_
                                         std::to_string(cap) + " states of " + std::to_string(lay.n_words) + " words)");
     }
     ForestParams& p = f->p;
-    p.pos = static_cast<uint8_t*>(pos.ptr);
-    p.pos_stride = pos.stride[0];
-    p.pos_agent_stride = pos.ndim > 2 ? pos.stride[1] : 2;
-    p.bits = static_cast<uint64_t*>(bits.ptr);
-    p.gems = static_cast<uint32_t*>(gems.ptr);
-    p.beams = static_cast<uint32_t*>(beams.ptr);
-    p.beam_stride = beams.stride[0];
-    p.avail = static_cast<uint8_t*>(avail.ptr);
-    p.avail_stride = avail.stride[0];
-    p.actions = static_cast<uint8_t*>(actions.ptr);
-    p.act_stride = actions.stride[0];
-    p.err = static_cast<const uint8_t*>(errs.ptr);
     p.pool = f->d_pool;
     p.parent = f->d_parent;
     p.action = f->d_action;
@@ -576,14 +439,9 @@ int lle_forest_run(lle_forest* f, const lle_search_args* args, lle_forest_result
         mr.expanded.clear();
         mr.plan.clear();
         const uint32_t* root = f->roots.data() + m * (size_t)r.n_words;
-        bool root_ok = !sl::anybody_dead(root[r.w_bits], A);
-        if (root_ok && args->mode == LLE_SEARCH_NO_COOPERATION)
-            for (int a = 0; a < A; a++) {
-                const uint32_t word = root[2 * a / 4];
-                const int i = (word >> (8 * (2 * a % 4))) & 255, j = (word >> (8 * (2 * a % 4) + 8)) & 255;
-                if (i < p.H && j < p.W && sl::on_foreign_beam(f->foreign[m * HW + (size_t)i * p.W + j], a)) root_ok = false;
-            }
-        const bool solved = root_ok && sl::all_arrived(root[r.w_bits], A) && (!collect || sl::all_gems(root[r.w_gems], p.G));
+        const bool root_ok = !sl::anybody_dead(root[r.w_bits], A) &&
+                             !(args->mode == LLE_SEARCH_NO_COOPERATION && sl::root_on_foreign_beam(root, r, f->foreign.data() + m * HW, p.H, p.W));
+        const bool solved = root_ok && sl::is_goal(root[r.w_bits], root[r.w_gems], r, collect, p.G);
         mr.progress = fl::fresh_progress(root_ok && !solved);  // (not ok: no plan starts here)
         if (solved) mr.progress.length = 0;
         any_active = any_active || mr.progress.active;
@@ -741,7 +599,7 @@ int lle_forest_occupancy(const lle_forest* f, int64_t* valid_items, int64_t* lau
     return LLE_OK;
 }
 
-size_t lle_forest_debug_launched(char* buf, size_t cap) { return names_out(g_launched.load(), buf, cap); }
-size_t lle_forest_debug_compiled(char* buf, size_t cap) { return names_out((1u << K_COUNT) - 1u, buf, cap); }
+size_t lle_forest_debug_launched(char* buf, size_t cap) { return sd::names_out(KERNEL_NAMES, K_COUNT, g_launched.load(), buf, cap); }
+size_t lle_forest_debug_compiled(char* buf, size_t cap) { return sd::names_out(KERNEL_NAMES, K_COUNT, (1u << K_COUNT) - 1u, buf, cap); }
 
 }  // extern "C"

@@ -74,13 +74,7 @@ LLE_SEARCH_HD uint64_t state_index(int64_t map, uint64_t cap, uint64_t s) { retu
 LLE_SEARCH_HD uint64_t table_base(int64_t map, uint64_t slots) { return (uint64_t)map * slots; }
 LLE_SEARCH_HD uint64_t counter_index(int64_t map, int which) { return (uint64_t)map * N_COUNTERS + (uint64_t)which; }
 LLE_SEARCH_HD uint64_t foreign_base(int64_t map, int H, int W) { return (uint64_t)map * (uint64_t)H * (uint64_t)W; }
-// A power of two >= max(2 cap, cap + E + 1): room for the candidates of one piece beside a full pool.
-LLE_SEARCH_HD uint64_t table_slots(uint64_t cap, uint64_t E) {
-    const uint64_t want = 2 * cap > cap + E + 1 ? 2 * cap : cap + E + 1;
-    uint64_t slots = 8;
-    while (slots < want) slots <<= 1;
-    return slots;
-}
+using lle_search_logic::table_slots;  // (cap, E): a map's table segment is the single search's table with chunk = E
 
 // ---- the host's view of one map during a run
 enum { FATE_CONTINUE = 0, FATE_SOLVED, FATE_EMPTY, FATE_CAPACITY, FATE_STEP_ERROR };

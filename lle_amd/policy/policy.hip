@@ -17,6 +17,10 @@
 //                      successor's value costs a pass, never the result; the last pass changes nothing and so has read final values.
 //   lookup             policy_lookup, a lane per environment of the caller's batch: record, hash, find, exactness rule, digits
 // Global atomics are 32 bits wide throughout; counters that may pass 2^32 are two words with a carry (add64).
+//
+// The record I/O between a batch, the pool and a table slot (scatter_item, occupant_is, copy_record) is the search's, in
+// ../search/search_logic.hpp; error string, device guard, batch binding and the reset state are in ../search/search_device.hpp.  This
+// file's own: add64, depth and value, the relaxation, the lookup, the map fingerprint and the cache of callers' batches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,36 +32,21 @@
 #include <vector>
 
 #include "../../include/lle_policy.h"
+#include "../search/search_device.hpp"
 #include "policy_logic.hpp"
 
 namespace lle {
 
 namespace sl = lle_search_logic;
+namespace sd = lle_search_device;
 namespace pl = lle_policy_logic;
 
 constexpr int POLICY_THREADS = 256;
 // counters: 32-bit words; the *_LO / *_HI pairs are 64-bit counts
 enum { CNT_STATES = 0, CNT_OVERFLOW, CNT_CHANGED, CNT_SATURATED, CNT_EXPANDED_LO, CNT_EXPANDED_HI, CNT_ERRORS_LO, CNT_ERRORS_HI, CNT_COUNT };
 
-// The buffers of a batch that hold a state's identity (include/lle_hip.h descriptors, strides in elements).
-struct StateView {
-    const uint8_t* pos;     // LLE_BUF_POS
-    const uint64_t* bits;   // LLE_BUF_BITS
-    const uint32_t* gems;   // LLE_BUF_GEMS
-    const uint32_t* beams;  // LLE_BUF_BEAMS
-    int64_t pos_stride, pos_agent_stride, beam_stride;
-};
-
 struct PolicyParams {
-    // the handle's batch
-    uint8_t* pos;
-    uint64_t* bits;
-    uint32_t* gems;
-    uint32_t* beams;
-    uint8_t* avail;        // LLE_BUF_AVAIL
-    uint8_t* actions;      // LLE_BUF_ACTIONS
-    const uint8_t* err;    // LLE_BUF_ERR
-    int64_t pos_stride, pos_agent_stride, beam_stride, avail_stride, act_stride;  // elements
+    sl::BatchView b;       // the handle's batch (include/lle_hip.h buffer descriptors, read once)
     // the handle
     uint32_t* pool;        // [n_words][max_states]
     uint16_t* depth;       // [max_states]
@@ -80,7 +69,7 @@ struct PolicyParams {
 };
 
 struct LookupParams {
-    StateView env;         // the caller's batch
+    sl::KeyView env;       // the caller's batch
     int64_t n_envs;
     const uint32_t* pool;
     const uint16_t* depth;
@@ -101,78 +90,18 @@ __device__ inline void add64(uint32_t* counters, int lo, uint32_t n) {
     if (old + n < old) atomicAdd(&counters[lo + 1], 1u);
 }
 
-// Identity word w (< w_gems + 1) of the record in environment k of a batch.
-__device__ inline uint32_t env_key_word(const StateView& v, const sl::RecordLayout& r, int64_t k, int w) {
-    if (w < r.n_pos) {
-        uint32_t x = 0u;
-        for (int b = 0; b < 4; b++) {
-            const int byte = 4 * w + b;
-            if (byte < 2 * r.A) x |= (uint32_t)v.pos[k * v.pos_stride + (byte >> 1) * v.pos_agent_stride + (byte & 1)] << (8 * b);
-        }
-        return x;
-    }
-    if (w == r.w_bits) return (uint32_t)v.bits[k];
-    if (w == r.w_bits + 1) return (uint32_t)(v.bits[k] >> 32);
-    if (w < r.w_gems) return v.beams[k * v.beam_stride + (w - r.w_beams)];
-    return v.gems[k];
-}
-
-// Word w of the record in environment k of the handle's batch.
-struct EnvRecord {
-    const PolicyParams& p;
-    int64_t k;
-    __device__ uint32_t operator()(int w) const {
-        const sl::RecordLayout& r = p.lay;
-        if (w <= r.w_gems) return env_key_word(StateView{p.pos, p.bits, p.gems, p.beams, p.pos_stride, p.pos_agent_stride, p.beam_stride}, r, k, w);
-        uint32_t v = 0u;
-        for (int b = 0; b < 4; b++) {
-            const int a = 4 * (w - r.w_avail) + b;
-            if (a < r.A) v |= (uint32_t)p.avail[k * p.avail_stride + a] << (8 * b);
-        }
-        return v;
-    }
-};
-// Word w of state s of the pool.
-struct PoolRecord {
-    const uint32_t* pool;
-    uint32_t max_states, s;
-    __device__ uint32_t operator()(int w) const { return pool[(size_t)w * max_states + s]; }
-};
-
-__device__ inline uint32_t relaxed_load(const uint32_t* at) { return __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+using sd::relaxed_load;
 
 // search_expand with a block-wide count: lane k scatters the record of its state into environment k and writes its joint action.
 __global__ __launch_bounds__(POLICY_THREADS) void policy_expand(PolicyParams p) {
     const uint32_t k = blockIdx.x * POLICY_THREADS + threadIdx.x;
     bool valid = false;
     if (k < p.n_items) {
-        const sl::RecordLayout& r = p.lay;
         const uint64_t item = p.item0 + k;
         const uint32_t s = p.first_state + (uint32_t)(item / p.n_joint);  // < the level's end <= max_states
-        const uint32_t code = (uint32_t)(item % p.n_joint);
-        const PoolRecord rec{p.pool, p.max_states, s};
-        uint32_t av[2] = {rec(r.w_avail), r.n_av > 1 ? rec(r.w_avail + 1) : 0u};
-        auto avail = [&](int a) { return (av[a >> 2] >> (8 * (a & 3))) & 255u; };
-        valid = sl::joint_available(code, r.A, avail);
+        // (an invalid item leaves environment k as it is: whatever the step makes of it, the kernels behind drop the item)
+        valid = sl::scatter_item(p.b, p.lay, sl::PoolRecord{p.pool, p.max_states, s}, k, (uint32_t)(item % p.n_joint));
         p.valid[k] = valid ? 1 : 0;
-        if (valid) {  // (an invalid item leaves environment k as it is: whatever the step makes of it, the kernels behind drop the item)
-            for (int w = 0; w < r.n_pos; w++) {
-                const uint32_t v = rec(w);
-                for (int b = 0; b < 4; b++) {
-                    const int byte = 4 * w + b;
-                    if (byte < 2 * r.A) p.pos[(int64_t)k * p.pos_stride + (byte >> 1) * p.pos_agent_stride + (byte & 1)] = (uint8_t)(v >> (8 * b));
-                }
-            }
-            p.bits[k] = (uint64_t)rec(r.w_bits) | (uint64_t)rec(r.w_bits + 1) << 32;
-            for (int w = 0; w < r.Lw; w++) p.beams[(int64_t)k * p.beam_stride + w] = rec(r.w_beams + w);
-            p.gems[k] = rec(r.w_gems);
-            uint32_t digits = code;
-            for (int a = 0; a < r.A; a++) {
-                p.avail[(int64_t)k * p.avail_stride + a] = (uint8_t)avail(a);
-                p.actions[(int64_t)k * p.act_stride + a] = (uint8_t)(digits % 5u);
-                digits /= 5u;
-            }
-        }
     }
     if (p.count_expanded) {  // (uniform over the grid: every thread of the block reaches the barrier)
         const int n = __syncthreads_count(valid ? 1 : 0);
@@ -187,32 +116,17 @@ __global__ __launch_bounds__(POLICY_THREADS) void policy_insert(PolicyParams p) 
     p.win_slot[k] = sl::SLOT_EMPTY;
     if (relaxed_load(&p.counters[CNT_OVERFLOW]) != 0u) return;  // (set by an earlier launch: the build has failed already)
     if (!p.valid[k]) return;
-    if (p.err[k] != 0) {  // the step refused a joint action the mask allowed
+    if (p.b.err[k] != 0) {  // the step refused a joint action the mask allowed
         add64(p.counters, CNT_ERRORS_LO, 1u);
         return;
     }
     const sl::RecordLayout& r = p.lay;
-    const EnvRecord me{p, (int64_t)k};
+    const sl::EnvRecord me{p.b, r, k};
     if (sl::anybody_dead(me(r.w_bits), r.A)) return;
     const uint64_t h = sl::hash_record(me, r.n_key);
-    auto load = [](uint32_t* slot) { return relaxed_load(slot); };
-    auto cas = [](uint32_t* slot, uint32_t expected, uint32_t desired) { return atomicCAS(slot, expected, desired); };
-    auto same_as = [&](uint32_t occupant) {
-        if (occupant & sl::TAG_BIT) {
-            const uint32_t other = occupant & ~sl::TAG_BIT;
-            if (other >= p.n_items) return false;  // (no such tag in a sound table)
-            const EnvRecord rec{p, (int64_t)other};
-            for (int w = 0; w < r.n_key; w++)
-                if (rec(w) != me(w)) return false;
-            return true;
-        }
-        if (occupant >= p.max_states) return false;
-        const PoolRecord rec{p.pool, p.max_states, occupant};
-        for (int w = 0; w < r.n_key; w++)
-            if (rec(w) != me(w)) return false;
-        return true;
-    };
-    const int64_t slot = sl::table_insert(p.table, p.table_mask, h, sl::TAG_BIT | k, load, cas, same_as);
+    const sl::Occupants who{p.b.key(), 0, p.n_items, p.pool, p.max_states, p.max_states};
+    auto same_as = [&](uint32_t occupant) { return sl::occupant_is(who, r, occupant, me); };
+    const int64_t slot = sl::table_insert(p.table, p.table_mask, h, sl::TAG_BIT | k, sd::SlotLoad{}, sd::SlotCas{}, same_as);
     if (slot >= 0) p.win_slot[k] = (uint32_t)slot;
     else if (slot == sl::INSERT_FULL) atomicMax(&p.counters[CNT_OVERFLOW], 1u);
 }
@@ -229,9 +143,9 @@ __global__ __launch_bounds__(POLICY_THREADS) void policy_commit(PolicyParams p) 
         return;
     }
     const sl::RecordLayout& r = p.lay;
-    const EnvRecord me{p, (int64_t)k};
-    for (int w = 0; w < r.n_words; w++) p.pool[(size_t)w * p.max_states + idx] = me(w);
-    const bool goal = sl::all_arrived(me(r.w_bits), r.A) && (!p.collect_gems || sl::all_gems(me(r.w_gems), p.G));
+    const sl::EnvRecord me{p.b, r, k};
+    sl::copy_record(p.b, r, k, p.pool, p.max_states, idx);
+    const bool goal = sl::is_goal(me(r.w_bits), me(r.w_gems), r, p.collect_gems != 0u, p.G);
     p.depth[idx] = (uint16_t)(p.level + 1u);
     p.value[idx] = goal ? pl::pack_value(0u, pl::stay_code(r.A)) : pl::NO_PLAN;
     p.table[slot] = idx;
@@ -241,19 +155,14 @@ __global__ __launch_bounds__(POLICY_THREADS) void policy_commit(PolicyParams p) 
 __global__ __launch_bounds__(POLICY_THREADS) void policy_relax(PolicyParams p) {
     const uint32_t k = blockIdx.x * POLICY_THREADS + threadIdx.x;
     if (k >= p.n_items) return;
-    if (!p.valid[k] || p.err[k] != 0) return;  // (refusals were counted by the exploration)
+    if (!p.valid[k] || p.b.err[k] != 0) return;  // (refusals were counted by the exploration)
     const sl::RecordLayout& r = p.lay;
-    const EnvRecord me{p, (int64_t)k};
+    const sl::EnvRecord me{p.b, r, k};
     if (sl::anybody_dead(me(r.w_bits), r.A)) return;
     const uint64_t h = sl::hash_record(me, r.n_key);
     auto load = [](const uint32_t* slot) { return *slot; };  // (the table is immutable now)
-    auto same_as = [&](uint32_t occupant) {
-        if (occupant >= p.max_states) return false;
-        const PoolRecord rec{p.pool, p.max_states, occupant};
-        for (int w = 0; w < r.n_key; w++)
-            if (rec(w) != me(w)) return false;
-        return true;
-    };
+    const sl::Occupants who{p.b.key(), 0, 0u, p.pool, p.max_states, p.max_states};
+    auto same_as = [&](uint32_t occupant) { return sl::occupant_is(who, r, occupant, me); };
     const int64_t succ = pl::table_find(p.table, p.table_mask, h, load, same_as);
     if (succ == pl::FIND_MISSING) return;
     const uint64_t item = p.item0 + k;
@@ -272,20 +181,15 @@ __global__ __launch_bounds__(POLICY_THREADS) void policy_lookup(LookupParams q) 
     const int64_t e = (int64_t)blockIdx.x * POLICY_THREADS + threadIdx.x;
     if (e >= q.n_envs) return;
     const sl::RecordLayout& r = q.lay;
-    auto key = [&](int w) { return env_key_word(q.env, r, e, w); };  // (read again for the comparison: n_key <= w_gems + 1 words, in cache)
+    auto key = [&](int w) { return sl::env_word(q.env, r, e, w); };  // (read again for the comparison: n_key <= w_gems + 1 words, in cache)
     int32_t answer = pl::ANSWER_DEAD_END;
     uint32_t code = pl::stay_code(r.A);
     if (!sl::anybody_dead(key(r.w_bits), r.A)) {
         answer = pl::ANSWER_UNKNOWN;
         const uint64_t h = sl::hash_record(key, r.n_key);
         auto load = [](const uint32_t* slot) { return *slot; };
-        auto same_as = [&](uint32_t occupant) {
-            if (occupant >= q.n_states) return false;
-            const PoolRecord rec{q.pool, q.max_states, occupant};
-            for (int w = 0; w < r.n_key; w++)
-                if (rec(w) != key(w)) return false;
-            return true;
-        };
+        const sl::Occupants who{q.env, 0, 0u, q.pool, q.max_states, q.n_states};
+        auto same_as = [&](uint32_t occupant) { return sl::occupant_is(who, r, occupant, key); };
         const int64_t s = pl::table_find(q.table, q.table_mask, h, load, same_as);
         if (s != pl::FIND_MISSING) {
             const uint32_t v = q.value[(uint32_t)s];
@@ -308,49 +212,25 @@ using lle::LookupParams;
 using lle::PolicyParams;
 namespace sl = lle_search_logic;
 namespace pl = lle_policy_logic;
+namespace sd = lle_search_device;
+using sd::DeviceGuard;
+using sd::fail;
+using sd::g_error;
 
 namespace {
 
-thread_local std::string g_error;
 std::atomic<uint32_t> g_launched{0};
 constexpr int N_KERNELS = 5;
 const char* const KERNEL_NAMES[N_KERNELS] = {"policy_expand", "policy_insert", "policy_commit", "policy_relax", "policy_lookup"};
 enum { K_EXPAND = 1u, K_INSERT = 2u, K_COMMIT = 4u, K_RELAX = 8u, K_LOOKUP = 16u };
 
-int fail(int code, const std::string& why) {
-    g_error = why;
-    return code;
-}
-
-struct DeviceGuard {  // the handle's device current for the call, the caller's put back
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-size_t names_out(uint32_t bits, char* buf, size_t cap) {
-    std::string s;
-    for (int k = 0; k < N_KERNELS; k++)
-        if ((bits >> k) & 1u) s += std::string(KERNEL_NAMES[k]) + "\n";
-    if (buf && cap > 0) {
-        const size_t n = std::min(cap - 1, s.size());
-        std::memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return s.size() + 1;
-}
+static_assert(LLE_POLICY_MAX_AGENTS == sl::MAX_AGENTS, "include/lle_policy.h and search_logic.hpp disagree");
 
 // What a lookup keeps about a caller's batch.
 struct BatchEntry {
     const lle_batch* batch = nullptr;
     lle_buffer_desc pos{}, beams{};  // as queried: compared at every call
-    lle::StateView view{};
+    sl::KeyView view{};
     int64_t n_envs = 0;
 };
 
@@ -449,38 +329,6 @@ int read_counters(lle_policy* s, uint32_t* counters) {
 
 uint64_t pair64(const uint32_t* counters, int lo) { return (uint64_t)counters[lo] | (uint64_t)counters[lo + 1] << 32; }
 
-// The record of environment 0 of the handle's batch, copied to the host (synchronises).
-int read_root(lle_policy* s) {
-    const PolicyParams& p = s->p;
-    const sl::RecordLayout r = sl::make_layout(s->info.n_agents, s->info.n_beam_words, false);
-    const int A = r.A;
-    std::vector<uint8_t> pos((size_t)std::max<int64_t>(1, p.pos_stride)), avail((size_t)std::max<int64_t>(1, p.avail_stride));
-    std::vector<uint32_t> beams((size_t)std::max(1, r.Lw));
-    uint64_t bits = 0;
-    uint32_t gems = 0;
-    bool ok = hipMemcpyAsync(pos.data(), p.pos, pos.size(), hipMemcpyDeviceToHost, s->stream) == hipSuccess &&
-              hipMemcpyAsync(avail.data(), p.avail, avail.size(), hipMemcpyDeviceToHost, s->stream) == hipSuccess &&
-              hipMemcpyAsync(&bits, p.bits, 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess &&
-              hipMemcpyAsync(&gems, p.gems, 4, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-    if (ok && r.Lw > 0) ok = hipMemcpyAsync(beams.data(), p.beams, (size_t)r.Lw * 4, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-    if (!ok || hipStreamSynchronize(s->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(LLE_ERR_HIP, "reading the reset state failed");
-    }
-    s->root.assign((size_t)r.n_words, 0u);
-    for (int a = 0; a < A; a++)
-        for (int c = 0; c < 2; c++) {
-            const int byte = 2 * a + c;
-            s->root[(size_t)(byte / 4)] |= (uint32_t)pos[(size_t)(a * p.pos_agent_stride + c)] << (8 * (byte % 4));
-        }
-    s->root[(size_t)r.w_bits] = (uint32_t)bits;
-    s->root[(size_t)r.w_bits + 1] = (uint32_t)(bits >> 32);
-    for (int w = 0; w < r.Lw; w++) s->root[(size_t)(r.w_beams + w)] = beams[(size_t)w];
-    s->root[(size_t)r.w_gems] = gems;
-    for (int a = 0; a < A; a++) s->root[(size_t)(r.w_avail + a / 4)] |= (uint32_t)avail[(size_t)a] << (8 * (a % 4));
-    return LLE_OK;
-}
-
 // FNV-1a over the bytes of 64-bit values, finished with the search's mixer.
 struct Fingerprint {
     uint64_t h = 0xCBF29CE484222325ull;
@@ -572,27 +420,12 @@ lle_policy* lle_policy_create(const lle_map* map, const lle_policy_options* opt)
         fail(LLE_ERR_ARG, "lle_map_get_info failed");
         return nullptr;
     }
-    if (info.n_agents > LLE_POLICY_MAX_AGENTS || info.n_agents < 1) {
-        fail(LLE_ERR_UNSUPPORTED, "more than 6 agents: a state has 5^A joint actions, the table serves maps of at most 6 agents (this map has " +
-                                      std::to_string(info.n_agents) + ")");
+    if (!sd::record_limits_ok(
+            info, "more than 6 agents: a state has 5^A joint actions, the table serves maps of at most 6 agents (this map has "))
         return nullptr;
-    }
-    if (info.n_beam_words > sl::MAX_BEAM_WORDS || info.n_beam_words < 0 || info.n_gems > 32) {
-        fail(LLE_ERR_UNSUPPORTED, "more beam words or gems than a state record holds");
+    int device = -1;
+    if (sd::choose_device(opt ? opt->device : -1, "no HIP device: the table is built on the GPU only (there is no CPU fallback)", &device) != LLE_OK)
         return nullptr;
-    }
-    int n_devices = 0;
-    if (hipGetDeviceCount(&n_devices) != hipSuccess || n_devices <= 0) {
-        (void)hipGetLastError();
-        fail(LLE_ERR_NO_DEVICE, "no HIP device: the table is built on the GPU only (there is no CPU fallback)");
-        return nullptr;
-    }
-    int device = opt ? opt->device : -1;
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-    if (device >= n_devices) {
-        fail(LLE_ERR_ARG, "no such HIP device");
-        return nullptr;
-    }
     auto* s = new lle_policy();
     s->device = device;
     s->stream = reinterpret_cast<hipStream_t>(opt ? opt->stream : nullptr);
@@ -606,26 +439,12 @@ lle_policy* lle_policy_create(const lle_map* map, const lle_policy_options* opt)
         lle_policy_free(s);
         return nullptr;
     }
-    lle_buffer_desc pos{}, bits{}, gems{}, beams{}, avail{}, actions{}, errs{};
-    if (lle_batch_get_buffer(s->batch, LLE_BUF_POS, &pos) || lle_batch_get_buffer(s->batch, LLE_BUF_BITS, &bits) ||
-        lle_batch_get_buffer(s->batch, LLE_BUF_GEMS, &gems) || lle_batch_get_buffer(s->batch, LLE_BUF_BEAMS, &beams) ||
-        lle_batch_get_buffer(s->batch, LLE_BUF_AVAIL, &avail) || lle_batch_get_buffer(s->batch, LLE_BUF_ACTIONS, &actions) ||
-        lle_batch_get_buffer(s->batch, LLE_BUF_ERR, &errs)) {
-        fail(LLE_ERR_ARG, "lle_batch_get_buffer failed");
-        lle_policy_free(s);
-        return nullptr;
-    }
-    if (pos.elem_bytes != 1 || bits.elem_bytes != 8 || gems.elem_bytes != 4 || beams.elem_bytes != 4 || avail.elem_bytes != 1 || actions.elem_bytes != 1 ||
-        errs.elem_bytes != 1 || pos.stride[0] < 2 * info.n_agents || avail.stride[0] < info.n_agents || actions.stride[0] < info.n_agents ||
-        beams.stride[0] < info.n_beam_words) {
-        fail(LLE_ERR_UNSUPPORTED, "the batch's buffers do not have the layout include/lle_hip.h describes");
+    if (sd::bind_batch(s->batch, info, chunk, &s->p.b) != LLE_OK) {
         lle_policy_free(s);
         return nullptr;
     }
     const sl::RecordLayout lay = sl::make_layout(info.n_agents, info.n_beam_words, false);
-    // a power of two >= 2 * max_states with room for the candidates of one piece beside a full pool
-    uint64_t slots = 8;
-    while (slots < std::max<uint64_t>(2 * (uint64_t)max_states, (uint64_t)max_states + (uint64_t)chunk + 1)) slots <<= 1;
+    const uint64_t slots = sl::table_slots((uint64_t)max_states, (uint64_t)chunk);
     if (hipMalloc(&s->d_pool, (size_t)lay.n_words * (size_t)max_states * 4) != hipSuccess || hipMalloc(&s->d_depth, (size_t)max_states * 2) != hipSuccess ||
         hipMalloc(&s->d_value, (size_t)max_states * 4) != hipSuccess || hipMalloc(&s->d_table, (size_t)slots * 4) != hipSuccess ||
         hipMalloc(&s->d_valid, (size_t)chunk) != hipSuccess || hipMalloc(&s->d_win, (size_t)chunk * 4) != hipSuccess ||
@@ -637,18 +456,6 @@ lle_policy* lle_policy_create(const lle_map* map, const lle_policy_options* opt)
         return nullptr;
     }
     PolicyParams& p = s->p;
-    p.pos = static_cast<uint8_t*>(pos.ptr);
-    p.pos_stride = pos.stride[0];
-    p.pos_agent_stride = pos.ndim > 2 ? pos.stride[1] : 2;
-    p.bits = static_cast<uint64_t*>(bits.ptr);
-    p.gems = static_cast<uint32_t*>(gems.ptr);
-    p.beams = static_cast<uint32_t*>(beams.ptr);
-    p.beam_stride = beams.stride[0];
-    p.avail = static_cast<uint8_t*>(avail.ptr);
-    p.avail_stride = avail.stride[0];
-    p.actions = static_cast<uint8_t*>(actions.ptr);
-    p.act_stride = actions.stride[0];
-    p.err = static_cast<const uint8_t*>(errs.ptr);
     p.pool = s->d_pool;
     p.depth = s->d_depth;
     p.value = s->d_value;
@@ -661,7 +468,7 @@ lle_policy* lle_policy_create(const lle_map* map, const lle_policy_options* opt)
     p.table_mask = (uint32_t)(slots - 1);
     p.G = info.n_gems;
     p.n_joint = sl::pow5(info.n_agents);
-    if (read_root(s) != LLE_OK) {  // the batch is freshly reset (World::new calls reset)
+    if (sd::read_root(p.b, lay, s->stream, &s->root) != LLE_OK) {  // the batch is freshly reset (World::new calls reset)
         lle_policy_free(s);
         return nullptr;
     }
@@ -697,21 +504,15 @@ int lle_policy_build(lle_policy* s, const lle_policy_args* args, lle_policy_resu
 
     // ---- pool, table and counters: the reset state is state 0, at depth 0
     const std::vector<uint32_t>& root = s->root;
-    const size_t slots = (size_t)p.table_mask + 1;
     uint32_t counters[lle::CNT_COUNT] = {};
     counters[lle::CNT_STATES] = 1;
-    const uint64_t h = sl::hash_record([&](int w) { return root[(size_t)w]; }, r.n_key);
-    const bool root_goal = !sl::anybody_dead(root[(size_t)r.w_bits], A) && sl::all_arrived(root[(size_t)r.w_bits], A) &&
-                           (!collect || sl::all_gems(root[(size_t)r.w_gems], p.G));
-    const uint32_t zero = 0u, root_value = root_goal ? pl::pack_value(0u, pl::stay_code(A)) : pl::NO_PLAN;
+    const bool root_goal = !sl::anybody_dead(root[(size_t)r.w_bits], A) && sl::is_goal(root[(size_t)r.w_bits], root[(size_t)r.w_gems], r, collect, p.G);
+    const uint32_t root_value = root_goal ? pl::pack_value(0u, pl::stay_code(A)) : pl::NO_PLAN;
     const uint16_t zero16 = 0;
-    bool ok = hipMemsetAsync(p.table, 0xFF, slots * 4, s->stream) == hipSuccess &&
-              hipMemcpyAsync(p.counters, counters, sizeof(counters), hipMemcpyHostToDevice, s->stream) == hipSuccess &&
-              hipMemcpyAsync(p.table + ((uint32_t)h & p.table_mask), &zero, 4, hipMemcpyHostToDevice, s->stream) == hipSuccess &&
-              hipMemcpyAsync(p.value, &root_value, 4, hipMemcpyHostToDevice, s->stream) == hipSuccess &&
-              hipMemcpyAsync(p.depth, &zero16, 2, hipMemcpyHostToDevice, s->stream) == hipSuccess;
-    for (int w = 0; ok && w < r.n_words; w++)
-        ok = hipMemcpyAsync(p.pool + (size_t)w * p.max_states, &root[(size_t)w], 4, hipMemcpyHostToDevice, s->stream) == hipSuccess;
+    const bool ok = sd::seed_root(p.table, p.table_mask, p.pool, p.max_states, root.data(), r, s->stream) &&
+                    hipMemcpyAsync(p.counters, counters, sizeof(counters), hipMemcpyHostToDevice, s->stream) == hipSuccess &&
+                    hipMemcpyAsync(p.value, &root_value, 4, hipMemcpyHostToDevice, s->stream) == hipSuccess &&
+                    hipMemcpyAsync(p.depth, &zero16, 2, hipMemcpyHostToDevice, s->stream) == hipSuccess;
     if (!ok || hipStreamSynchronize(s->stream) != hipSuccess) {  // (the sources are stack and handle memory: copied before they change)
         (void)hipGetLastError();
         return fail(LLE_ERR_HIP, "preparing the pool failed");
@@ -827,7 +628,7 @@ int lle_policy_lookup(lle_policy* s, const lle_batch* batch, int32_t* steps_out,
         b.pos = pos;
         b.beams = beams;
         b.n_envs = n;
-        b.view = lle::StateView{static_cast<const uint8_t*>(pos.ptr), static_cast<const uint64_t*>(bits.ptr), static_cast<const uint32_t*>(gems.ptr),
+        b.view = sl::KeyView{static_cast<const uint8_t*>(pos.ptr), static_cast<const uint64_t*>(bits.ptr), static_cast<const uint32_t*>(gems.ptr),
                                 static_cast<const uint32_t*>(beams.ptr), pos.stride[0], pos.stride[1], beams.stride[0]};
         if (s->batches.size() >= 64) s->batches.erase(s->batches.begin());  // (a bound, not a policy: entries are a few words)
         s->batches.push_back(b);
@@ -857,7 +658,7 @@ int lle_policy_lookup(lle_policy* s, const lle_batch* batch, int32_t* steps_out,
     return LLE_OK;
 }
 
-size_t lle_policy_debug_launched(char* buf, size_t cap) { return names_out(g_launched.load(), buf, cap); }
-size_t lle_policy_debug_compiled(char* buf, size_t cap) { return names_out((1u << N_KERNELS) - 1u, buf, cap); }
+size_t lle_policy_debug_launched(char* buf, size_t cap) { return sd::names_out(KERNEL_NAMES, N_KERNELS, g_launched.load(), buf, cap); }
+size_t lle_policy_debug_compiled(char* buf, size_t cap) { return sd::names_out(KERNEL_NAMES, N_KERNELS, (1u << N_KERNELS) - 1u, buf, cap); }
 
 }  // extern "C"

@@ -17,6 +17,11 @@
 //                   candidate the tag names, whose record lies complete in the batch since the step.  No lane waits for another.
 //   search_commit   every winner takes a pool index, copies its record, parent and action, and puts the index where its tag was
 // The host reads five counters once per level.
+//
+// What this file shares with ../forest/forest.hip and the steps-to-go library lives in two headers: search_logic.hpp (host and device:
+// record layout, hash, table, and the record I/O between a batch, a pool and a table slot) and search_device.hpp (HIP: error string,
+// device guard, batch binding, reset state, foreign-beam table).  Here are the counters, the LDS foreign table, the level loop and
+// the plan walk.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,26 +33,20 @@
 #include <vector>
 
 #include "../../include/lle_search.h"
+#include "search_device.hpp"
 #include "search_logic.hpp"
 
 namespace lle {
 
 namespace sl = lle_search_logic;
+namespace sd = lle_search_device;
 
 constexpr int SEARCH_THREADS = 256;
 enum { CNT_STATES = 0, CNT_EXPANDED, CNT_GOAL, CNT_OVERFLOW, CNT_STEP_ERRORS, CNT_COUNT = 8 };
 constexpr unsigned long long NO_GOAL = ~0ull;
 
 struct SearchParams {
-    // the batch (include/lle_hip.h buffer descriptors, read once)
-    uint8_t* pos;          // LLE_BUF_POS
-    uint64_t* bits;        // LLE_BUF_BITS
-    uint32_t* gems;        // LLE_BUF_GEMS
-    uint32_t* beams;       // LLE_BUF_BEAMS
-    uint8_t* avail;        // LLE_BUF_AVAIL
-    uint8_t* actions;      // LLE_BUF_ACTIONS
-    const uint8_t* err;    // LLE_BUF_ERR
-    int64_t pos_stride, pos_agent_stride, beam_stride, avail_stride, act_stride;  // elements
+    sl::BatchView b;       // the batch (include/lle_hip.h buffer descriptors, read once)
     // the handle
     uint32_t* pool;        // [n_words][max_states]
     uint32_t* parent;      // [max_states]
@@ -68,70 +67,15 @@ struct SearchParams {
     uint32_t n_items;      // <= chunk
 };
 
-// Word w of the record in environment k of the batch.
-struct EnvRecord {
-    const SearchParams& p;
-    int64_t k;
-    __device__ uint32_t operator()(int w) const {
-        const sl::RecordLayout& r = p.lay;
-        if (w < r.n_pos) {
-            uint32_t v = 0u;
-            for (int b = 0; b < 4; b++) {
-                const int byte = 4 * w + b;
-                if (byte < 2 * r.A) v |= (uint32_t)p.pos[k * p.pos_stride + (byte >> 1) * p.pos_agent_stride + (byte & 1)] << (8 * b);
-            }
-            return v;
-        }
-        if (w == r.w_bits) return (uint32_t)p.bits[k];
-        if (w == r.w_bits + 1) return (uint32_t)(p.bits[k] >> 32);
-        if (w < r.w_gems) return p.beams[k * p.beam_stride + (w - r.w_beams)];
-        if (w == r.w_gems) return p.gems[k];
-        uint32_t v = 0u;
-        for (int b = 0; b < 4; b++) {
-            const int a = 4 * (w - r.w_avail) + b;
-            if (a < r.A) v |= (uint32_t)p.avail[k * p.avail_stride + a] << (8 * b);
-        }
-        return v;
-    }
-};
-// Word w of state s of the pool.
-struct PoolRecord {
-    const SearchParams& p;
-    uint32_t s;
-    __device__ uint32_t operator()(int w) const { return p.pool[(size_t)w * p.max_states + s]; }
-};
-
 __global__ __launch_bounds__(SEARCH_THREADS) void search_expand(SearchParams p) {
     const uint32_t k = blockIdx.x * SEARCH_THREADS + threadIdx.x;
     bool valid = false;
     if (k < p.n_items) {
-        const sl::RecordLayout& r = p.lay;
         const uint64_t item = p.item0 + k;
         const uint32_t s = p.first_state + (uint32_t)(item / p.n_joint);  // < the frontier's end <= max_states
-        const uint32_t code = (uint32_t)(item % p.n_joint);
-        const PoolRecord rec{p, s};
-        uint32_t av[2] = {rec(r.w_avail), r.n_av > 1 ? rec(r.w_avail + 1) : 0u};
-        auto avail = [&](int a) { return (av[a >> 2] >> (8 * (a & 3))) & 255u; };
-        valid = sl::joint_available(code, r.A, avail);
+        // (an invalid item leaves environment k as it is: whatever the step makes of it, search_insert drops the item)
+        valid = sl::scatter_item(p.b, p.lay, sl::PoolRecord{p.pool, p.max_states, s}, k, (uint32_t)(item % p.n_joint));
         p.valid[k] = valid ? 1 : 0;
-        if (valid) {  // (an invalid item leaves environment k as it is: whatever the step makes of it, search_insert drops the item)
-            for (int w = 0; w < r.n_pos; w++) {
-                const uint32_t v = rec(w);
-                for (int b = 0; b < 4; b++) {
-                    const int byte = 4 * w + b;
-                    if (byte < 2 * r.A) p.pos[(int64_t)k * p.pos_stride + (byte >> 1) * p.pos_agent_stride + (byte & 1)] = (uint8_t)(v >> (8 * b));
-                }
-            }
-            p.bits[k] = (uint64_t)rec(r.w_bits) | (uint64_t)rec(r.w_bits + 1) << 32;
-            for (int w = 0; w < r.Lw; w++) p.beams[(int64_t)k * p.beam_stride + w] = rec(r.w_beams + w);
-            p.gems[k] = rec(r.w_gems);
-            uint32_t digits = code;
-            for (int a = 0; a < r.A; a++) {
-                p.avail[(int64_t)k * p.avail_stride + a] = (uint8_t)avail(a);
-                p.actions[(int64_t)k * p.act_stride + a] = (uint8_t)(digits % 5u);
-                digits /= 5u;
-            }
-        }
     }
     if (valid) atomicAdd(&p.counters[CNT_EXPANDED], 1ull);
 }
@@ -150,39 +94,24 @@ __global__ __launch_bounds__(SEARCH_THREADS) void search_insert(SearchParams p) 
     p.win_slot[k] = sl::SLOT_EMPTY;
     if (p.counters[CNT_OVERFLOW] != 0ull) return;  // (set by an earlier launch: the search has failed already)
     if (!p.valid[k]) return;
-    if (p.err[k] != 0) {  // the step refused a joint action the mask allowed
+    if (p.b.err[k] != 0) {  // the step refused a joint action the mask allowed
         atomicAdd(&p.counters[CNT_STEP_ERRORS], 1ull);
         return;
     }
     const sl::RecordLayout& r = p.lay;
-    const EnvRecord me{p, (int64_t)k};
+    const sl::EnvRecord me{p.b, r, k};
     if (sl::anybody_dead(me(r.w_bits), r.A)) return;
     if constexpr (NO_COOP) {
         for (int a = 0; a < r.A; a++) {
-            const uint8_t* q = p.pos + (int64_t)k * p.pos_stride + a * p.pos_agent_stride;
+            const uint8_t* q = p.b.pos + (int64_t)k * p.b.pos_stride + a * p.b.pos_agent_stride;
             const int i = q[0], j = q[1];
             if (i < p.H && j < p.W && sl::on_foreign_beam(lds_foreign[i * p.W + j], a)) return;
         }
     }
     const uint64_t h = sl::hash_record(me, r.n_key);
-    auto load = [](uint32_t* slot) { return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    auto cas = [](uint32_t* slot, uint32_t expected, uint32_t desired) { return atomicCAS(slot, expected, desired); };
-    auto same_as = [&](uint32_t occupant) {
-        if (occupant & sl::TAG_BIT) {
-            const uint32_t other = occupant & ~sl::TAG_BIT;
-            if (other >= p.n_items) return false;  // (no such tag in a sound table)
-            const EnvRecord rec{p, (int64_t)other};
-            for (int w = 0; w < r.n_key; w++)
-                if (rec(w) != me(w)) return false;
-            return true;
-        }
-        if (occupant >= p.max_states) return false;
-        const PoolRecord rec{p, occupant};
-        for (int w = 0; w < r.n_key; w++)
-            if (rec(w) != me(w)) return false;
-        return true;
-    };
-    const int64_t slot = sl::table_insert(p.table, p.table_mask, h, sl::TAG_BIT | k, load, cas, same_as);
+    const sl::Occupants who{p.b.key(), 0, p.n_items, p.pool, p.max_states, p.max_states};
+    auto same_as = [&](uint32_t occupant) { return sl::occupant_is(who, r, occupant, me); };
+    const int64_t slot = sl::table_insert(p.table, p.table_mask, h, sl::TAG_BIT | k, sd::SlotLoad{}, sd::SlotCas{}, same_as);
     if (slot >= 0) p.win_slot[k] = (uint32_t)slot;
     else if (slot == sl::INSERT_FULL) atomicMax(&p.counters[CNT_OVERFLOW], 1ull);
 }
@@ -198,13 +127,13 @@ __global__ __launch_bounds__(SEARCH_THREADS) void search_commit(SearchParams p) 
         return;
     }
     const sl::RecordLayout& r = p.lay;
-    const EnvRecord me{p, (int64_t)k};
-    for (int w = 0; w < r.n_words; w++) p.pool[(size_t)w * p.max_states + idx] = me(w);
+    const sl::EnvRecord me{p.b, r, k};
+    sl::copy_record(p.b, r, k, p.pool, p.max_states, idx);
     const uint64_t item = p.item0 + k;
     p.parent[idx] = p.first_state + (uint32_t)(item / p.n_joint);
     p.action[idx] = (uint16_t)(item % p.n_joint);
     p.table[slot] = (uint32_t)idx;
-    if (sl::all_arrived(me(r.w_bits), r.A) && (!p.collect_gems || sl::all_gems(me(r.w_gems), p.G))) atomicMin(&p.counters[CNT_GOAL], idx);
+    if (sl::is_goal(me(r.w_bits), me(r.w_gems), r, p.collect_gems != 0u, p.G)) atomicMin(&p.counters[CNT_GOAL], idx);
 }
 
 template __global__ void search_insert<false>(SearchParams);
@@ -215,63 +144,22 @@ template __global__ void search_insert<true>(SearchParams);
 // ================================================================================================ host side
 using lle::SearchParams;
 namespace sl = lle_search_logic;
+namespace sd = lle_search_device;
+using sd::DeviceGuard;
+using sd::fail;
+using sd::g_error;
 
 namespace {
 
-thread_local std::string g_error;
 std::atomic<uint32_t> g_launched{0};
 const char* const KERNEL_NAMES[4] = {"search_expand", "search_insert<false>", "search_insert<true>", "search_commit"};
-
-int fail(int code, const std::string& why) {
-    g_error = why;
-    return code;
-}
-
-struct DeviceGuard {  // the handle's device current for the call, the caller's put back
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-size_t names_out(uint32_t bits, char* buf, size_t cap) {
-    std::string s;
-    for (int k = 0; k < 4; k++)
-        if ((bits >> k) & 1u) s += std::string(KERNEL_NAMES[k]) + "\n";
-    if (buf && cap > 0) {
-        const size_t n = std::min(cap - 1, s.size());
-        std::memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return s.size() + 1;
-}
+static_assert(LLE_SEARCH_MAX_AGENTS == sl::MAX_AGENTS, "include/lle_search.h and search_logic.hpp disagree");
 
 // Host copy of the static map data the search needs.
 struct MapData {
     lle_map_info info{};
     std::vector<uint8_t> foreign;  // [H * W]
 };
-
-bool build_map(const lle_map* map, MapData& md, std::string& err) {
-    if (lle_map_get_info(map, &md.info) != LLE_OK) { err = "lle_map_get_info failed"; return false; }
-    const int H = md.info.height, W = md.info.width;
-    std::vector<lle_source_info> src((size_t)std::max(0, lle_map_sources(map, nullptr, 0)));
-    lle_map_sources(map, src.data(), (int)src.size());
-    md.foreign.assign((size_t)H * W, 0);
-    std::vector<lle_laser_tile> tiles((size_t)std::max(0, lle_map_laser_tiles(map, nullptr, 0)));
-    lle_map_laser_tiles(map, tiles.data(), (int)tiles.size());
-    for (const auto& t : tiles) {
-        if (t.i < 0 || t.i >= H || t.j < 0 || t.j >= W || t.laser_id < 0 || t.laser_id >= (int)src.size()) { err = "laser tile out of range"; return false; }
-        const int colour = src[(size_t)t.laser_id].agent_id;
-        md.foreign[(size_t)t.i * W + t.j] |= sl::foreign_bit(colour);
-    }
-    return true;
-}
 
 }  // namespace
 
@@ -315,38 +203,6 @@ int launch_piece(lle_search* s, const SearchParams& p) {
     hipLaunchKernelGGL(lle::search_commit, grid, block, 0, s->stream, p);
     if (hipGetLastError() != hipSuccess) return fail(LLE_ERR_HIP, "search_commit launch failed");
     g_launched.fetch_or(1u | (p.mode == LLE_SEARCH_NO_COOPERATION ? 4u : 2u) | 8u);
-    return LLE_OK;
-}
-
-// The record of environment 0 of the handle's batch, copied to the host (synchronises).
-int read_root(lle_search* s) {
-    const SearchParams& p = s->p;
-    const sl::RecordLayout r = sl::make_layout(s->map.info.n_agents, s->map.info.n_beam_words, false);
-    const int A = r.A;
-    std::vector<uint8_t> pos((size_t)std::max<int64_t>(1, p.pos_stride)), avail((size_t)std::max<int64_t>(1, p.avail_stride));
-    std::vector<uint32_t> beams((size_t)std::max(1, r.Lw));
-    uint64_t bits = 0;
-    uint32_t gems = 0;
-    bool ok = hipMemcpyAsync(pos.data(), p.pos, pos.size(), hipMemcpyDeviceToHost, s->stream) == hipSuccess &&
-              hipMemcpyAsync(avail.data(), p.avail, avail.size(), hipMemcpyDeviceToHost, s->stream) == hipSuccess &&
-              hipMemcpyAsync(&bits, p.bits, 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess &&
-              hipMemcpyAsync(&gems, p.gems, 4, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-    if (ok && r.Lw > 0) ok = hipMemcpyAsync(beams.data(), p.beams, (size_t)r.Lw * 4, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
-    if (!ok || hipStreamSynchronize(s->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(LLE_ERR_HIP, "reading the reset state failed");
-    }
-    s->root.assign((size_t)r.n_words, 0u);
-    for (int a = 0; a < A; a++)
-        for (int c = 0; c < 2; c++) {
-            const int byte = 2 * a + c;
-            s->root[(size_t)(byte / 4)] |= (uint32_t)pos[(size_t)(a * p.pos_agent_stride + c)] << (8 * (byte % 4));
-        }
-    s->root[(size_t)r.w_bits] = (uint32_t)bits;
-    s->root[(size_t)r.w_bits + 1] = (uint32_t)(bits >> 32);
-    for (int w = 0; w < r.Lw; w++) s->root[(size_t)(r.w_beams + w)] = beams[(size_t)w];
-    s->root[(size_t)r.w_gems] = gems;
-    for (int a = 0; a < A; a++) s->root[(size_t)(r.w_avail + a / 4)] |= (uint32_t)avail[(size_t)a] << (8 * (a % 4));
     return LLE_OK;
 }
 
@@ -443,32 +299,20 @@ lle_search* lle_search_create(const lle_map* map, const lle_search_options* opt)
         return nullptr;
     }
     MapData md;
-    std::string err;
-    if (!build_map(map, md, err)) {
-        fail(LLE_ERR_ARG, err);
+    if (lle_map_get_info(map, &md.info) != LLE_OK) {
+        fail(LLE_ERR_ARG, "lle_map_get_info failed");
         return nullptr;
     }
-    if (md.info.n_agents > LLE_SEARCH_MAX_AGENTS || md.info.n_agents < 1) {
-        fail(LLE_ERR_UNSUPPORTED, "more than 6 agents: a state has 5^A joint actions, the search serves maps of at most 6 agents (this map has " +
-                                      std::to_string(md.info.n_agents) + ")");
+    if (!sd::build_foreign(map, md.info.height, md.info.width, md.foreign)) {
+        fail(LLE_ERR_ARG, "laser tile out of range");
         return nullptr;
     }
-    if (md.info.n_beam_words > sl::MAX_BEAM_WORDS || md.info.n_gems > 32) {
-        fail(LLE_ERR_UNSUPPORTED, "more beam words or gems than a state record holds");
+    if (!sd::record_limits_ok(
+            md.info, "more than 6 agents: a state has 5^A joint actions, the search serves maps of at most 6 agents (this map has "))
         return nullptr;
-    }
-    int n_devices = 0;
-    if (hipGetDeviceCount(&n_devices) != hipSuccess || n_devices <= 0) {
-        (void)hipGetLastError();
-        fail(LLE_ERR_NO_DEVICE, "no HIP device: the search runs on the GPU only (there is no CPU fallback)");
+    int device = -1;
+    if (sd::choose_device(opt ? opt->device : -1, "no HIP device: the search runs on the GPU only (there is no CPU fallback)", &device) != LLE_OK)
         return nullptr;
-    }
-    int device = opt ? opt->device : -1;
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-    if (device >= n_devices) {
-        fail(LLE_ERR_ARG, "no such HIP device");
-        return nullptr;
-    }
     auto* s = new lle_search();
     s->device = device;
     s->stream = reinterpret_cast<hipStream_t>(opt ? opt->stream : nullptr);
@@ -482,26 +326,12 @@ lle_search* lle_search_create(const lle_map* map, const lle_search_options* opt)
         lle_search_free(s);
         return nullptr;
     }
-    lle_buffer_desc pos{}, bits{}, gems{}, beams{}, avail{}, actions{}, errs{};
-    if (lle_batch_get_buffer(s->batch, LLE_BUF_POS, &pos) || lle_batch_get_buffer(s->batch, LLE_BUF_BITS, &bits) ||
-        lle_batch_get_buffer(s->batch, LLE_BUF_GEMS, &gems) || lle_batch_get_buffer(s->batch, LLE_BUF_BEAMS, &beams) ||
-        lle_batch_get_buffer(s->batch, LLE_BUF_AVAIL, &avail) || lle_batch_get_buffer(s->batch, LLE_BUF_ACTIONS, &actions) ||
-        lle_batch_get_buffer(s->batch, LLE_BUF_ERR, &errs)) {
-        fail(LLE_ERR_ARG, "lle_batch_get_buffer failed");
-        lle_search_free(s);
-        return nullptr;
-    }
-    if (pos.elem_bytes != 1 || bits.elem_bytes != 8 || gems.elem_bytes != 4 || beams.elem_bytes != 4 || avail.elem_bytes != 1 || actions.elem_bytes != 1 ||
-        errs.elem_bytes != 1 || pos.stride[0] < 2 * md.info.n_agents || avail.stride[0] < md.info.n_agents || actions.stride[0] < md.info.n_agents ||
-        beams.stride[0] < md.info.n_beam_words) {
-        fail(LLE_ERR_UNSUPPORTED, "the batch's buffers do not have the layout include/lle_hip.h describes");
+    if (sd::bind_batch(s->batch, md.info, chunk, &s->p.b) != LLE_OK) {
         lle_search_free(s);
         return nullptr;
     }
     const sl::RecordLayout lay = sl::make_layout(md.info.n_agents, md.info.n_beam_words, false);
-    // a power of two >= 2 * max_states with room for the candidates of one piece beside a full pool
-    uint64_t slots = 8;
-    while (slots < std::max<uint64_t>(2 * (uint64_t)max_states, (uint64_t)max_states + (uint64_t)chunk + 1)) slots <<= 1;
+    const uint64_t slots = sl::table_slots((uint64_t)max_states, (uint64_t)chunk);
     const size_t HW = (size_t)md.info.height * md.info.width;
     if (hipMalloc(&s->d_pool, (size_t)lay.n_words * (size_t)max_states * 4) != hipSuccess || hipMalloc(&s->d_parent, (size_t)max_states * 4) != hipSuccess ||
         hipMalloc(&s->d_action, (size_t)max_states * 2) != hipSuccess || hipMalloc(&s->d_table, (size_t)slots * 4) != hipSuccess ||
@@ -516,18 +346,6 @@ lle_search* lle_search_create(const lle_map* map, const lle_search_options* opt)
         return nullptr;
     }
     SearchParams& p = s->p;
-    p.pos = static_cast<uint8_t*>(pos.ptr);
-    p.pos_stride = pos.stride[0];
-    p.pos_agent_stride = pos.ndim > 2 ? pos.stride[1] : 2;
-    p.bits = static_cast<uint64_t*>(bits.ptr);
-    p.gems = static_cast<uint32_t*>(gems.ptr);
-    p.beams = static_cast<uint32_t*>(beams.ptr);
-    p.beam_stride = beams.stride[0];
-    p.avail = static_cast<uint8_t*>(avail.ptr);
-    p.avail_stride = avail.stride[0];
-    p.actions = static_cast<uint8_t*>(actions.ptr);
-    p.act_stride = actions.stride[0];
-    p.err = static_cast<const uint8_t*>(errs.ptr);
     p.pool = s->d_pool;
     p.parent = s->d_parent;
     p.action = s->d_action;
@@ -543,7 +361,7 @@ lle_search* lle_search_create(const lle_map* map, const lle_search_options* opt)
     p.W = md.info.width;
     p.G = md.info.n_gems;
     p.n_joint = sl::pow5(md.info.n_agents);
-    if (read_root(s) != LLE_OK) {  // the batch is freshly reset (World::new calls reset)
+    if (sd::read_root(p.b, lay, s->stream, &s->root) != LLE_OK) {  // the batch is freshly reset (World::new calls reset)
         lle_search_free(s);
         return nullptr;
     }
@@ -577,34 +395,24 @@ int lle_search_run(lle_search* s, const lle_search_args* args, lle_search_result
 
     // ---- the reset state, judged on the host with the kernels' own functions
     const std::vector<uint32_t>& root = s->root;
-    bool root_ok = !sl::anybody_dead(root[(size_t)r.w_bits], A);
-    if (root_ok && args->mode == LLE_SEARCH_NO_COOPERATION)
-        for (int a = 0; a < A; a++) {
-            const uint32_t word = root[(size_t)(2 * a / 4)];
-            const int i = (word >> (8 * (2 * a % 4))) & 255, j = (word >> (8 * (2 * a % 4) + 8)) & 255;
-            if (i < p.H && j < p.W && sl::on_foreign_beam(s->map.foreign[(size_t)i * p.W + j], a)) root_ok = false;
-        }
-    if (!root_ok) return LLE_OK;  // no plan starts here
-    if (sl::all_arrived(root[(size_t)r.w_bits], A) && (!collect || sl::all_gems(root[(size_t)r.w_gems], p.G))) {
+    if (sl::anybody_dead(root[(size_t)r.w_bits], A) ||
+        (args->mode == LLE_SEARCH_NO_COOPERATION && sl::root_on_foreign_beam(root.data(), r, s->map.foreign.data(), p.H, p.W)))
+        return LLE_OK;  // no plan starts here
+    if (sl::is_goal(root[(size_t)r.w_bits], root[(size_t)r.w_gems], r, collect, p.G)) {
         s->length = result->length = 0;
         return LLE_OK;
     }
 
     // ---- pool, table and counters
-    const size_t slots = (size_t)p.table_mask + 1;
     unsigned long long counters[lle::CNT_COUNT] = {};
     counters[lle::CNT_STATES] = 1;
     counters[lle::CNT_GOAL] = lle::NO_GOAL;
-    const uint64_t h = sl::hash_record([&](int w) { return root[(size_t)w]; }, r.n_key);
-    const uint32_t zero = 0u, none = 0xFFFFFFFFu;
+    const uint32_t none = 0xFFFFFFFFu;
     const uint16_t zero16 = 0;
-    bool ok = hipMemsetAsync(p.table, 0xFF, slots * 4, s->stream) == hipSuccess &&
-              hipMemcpyAsync(p.counters, counters, sizeof(counters), hipMemcpyHostToDevice, s->stream) == hipSuccess &&
-              hipMemcpyAsync(p.table + ((uint32_t)h & p.table_mask), &zero, 4, hipMemcpyHostToDevice, s->stream) == hipSuccess &&
-              hipMemcpyAsync(p.parent, &none, 4, hipMemcpyHostToDevice, s->stream) == hipSuccess &&
-              hipMemcpyAsync(p.action, &zero16, 2, hipMemcpyHostToDevice, s->stream) == hipSuccess;
-    for (int w = 0; ok && w < r.n_words; w++)
-        ok = hipMemcpyAsync(p.pool + (size_t)w * p.max_states, &root[(size_t)w], 4, hipMemcpyHostToDevice, s->stream) == hipSuccess;
+    const bool ok = sd::seed_root(p.table, p.table_mask, p.pool, p.max_states, root.data(), r, s->stream) &&
+                    hipMemcpyAsync(p.counters, counters, sizeof(counters), hipMemcpyHostToDevice, s->stream) == hipSuccess &&
+                    hipMemcpyAsync(p.parent, &none, 4, hipMemcpyHostToDevice, s->stream) == hipSuccess &&
+                    hipMemcpyAsync(p.action, &zero16, 2, hipMemcpyHostToDevice, s->stream) == hipSuccess;
     if (!ok || hipStreamSynchronize(s->stream) != hipSuccess) {  // (the sources are stack and handle memory: copied before they change)
         (void)hipGetLastError();
         return fail(LLE_ERR_HIP, "preparing the pool failed");
@@ -691,7 +499,7 @@ int lle_search_stats(const lle_search* s, int64_t* frontier, int64_t* expanded, 
     return (int)s->frontier.size();
 }
 
-size_t lle_search_debug_launched(char* buf, size_t cap) { return names_out(g_launched.load(), buf, cap); }
-size_t lle_search_debug_compiled(char* buf, size_t cap) { return names_out(0xFu, buf, cap); }
+size_t lle_search_debug_launched(char* buf, size_t cap) { return sd::names_out(KERNEL_NAMES, 4, g_launched.load(), buf, cap); }
+size_t lle_search_debug_compiled(char* buf, size_t cap) { return sd::names_out(KERNEL_NAMES, 4, 0xFu, buf, cap); }
 
 }  // extern "C"

@@ -1,6 +1,9 @@
 // search_logic.hpp -- the parts of the shortest-plan search (search.hip, liblle_search.so) that run the same on the host and on the
-// device: the layout of a state record, its hash, one probe step of the open-addressing table and what a record means (dead agent,
-// everybody arrived, an agent on a foreign beam).  tests/hostsim/search_table.cpp drives the table code under sanitizers.
+// device: the layout of a state record, its hash, one probe step of the open-addressing table, what a record means (dead agent,
+// everybody arrived, an agent on a foreign beam) and the record I/O: how a record is read out of and written into the buffers of a
+// batch (BatchView, env_word, scatter_item, copy_record), how it lies in a pool (PoolRecord) and whom a table slot names
+// (occupant_is).  ../forest/forest.hip and the steps-to-go library use the same code; search_device.hpp holds what needs HIP.
+// tests/hostsim/search_table.cpp drives the table code under sanitizers, tests/hostsim/record_io.cpp the record I/O.
 //
 // A RECORD is the dynamic state of one environment as 32-bit words, the identity first:
 //   [0, n_pos)              LLE_BUF_POS: the 2 A position bytes (i, j per agent), little-endian, zero padded
@@ -22,6 +25,7 @@
 
 namespace lle_search_logic {
 
+constexpr int MAX_AGENTS = 6;                  // LLE_SEARCH_MAX_AGENTS: 5^A joint actions fit 16 bits, the availability bytes two words
 constexpr int MAX_BEAM_WORDS = 32;             // LLE_MAX_BEAM_WORDS
 constexpr int MAX_RECORD_WORDS = 3 + 2 + MAX_BEAM_WORDS + 1 + 2;  // 40
 constexpr uint32_t SLOT_EMPTY = 0xFFFFFFFFu;   // a table slot nobody has claimed
@@ -129,6 +133,146 @@ LLE_SEARCH_HD uint32_t pow5(int A) {
     uint32_t p = 1;
     for (int a = 0; a < A; a++) p *= 5u;
     return p;
+}
+
+// A power of two >= max(2 cap, cap + chunk + 1): at most half full, with room for the candidates of one piece beside a full pool.
+LLE_SEARCH_HD uint64_t table_slots(uint64_t cap, uint64_t chunk) {
+    const uint64_t want = 2 * cap > cap + chunk + 1 ? 2 * cap : cap + chunk + 1;
+    uint64_t slots = 8;
+    while (slots < want) slots <<= 1;
+    return slots;
+}
+
+// ---- record I/O: a batch as include/lle_hip.h describes its buffers (pointers to environment 0, strides in elements)
+struct KeyView {  // the buffers that hold a state's identity, read only: all a lookup in somebody else's batch needs
+    const uint8_t* pos;     // LLE_BUF_POS
+    const uint64_t* bits;   // LLE_BUF_BITS
+    const uint32_t* gems;   // LLE_BUF_GEMS
+    const uint32_t* beams;  // LLE_BUF_BEAMS
+    int64_t pos_stride, pos_agent_stride, beam_stride;
+};
+struct BatchView {
+    uint8_t* pos;
+    uint64_t* bits;
+    uint32_t* gems;
+    uint32_t* beams;
+    uint8_t* avail;         // LLE_BUF_AVAIL
+    uint8_t* actions;       // LLE_BUF_ACTIONS
+    const uint8_t* err;     // LLE_BUF_ERR
+    int64_t pos_stride, pos_agent_stride, beam_stride, avail_stride, act_stride;
+    LLE_SEARCH_HD KeyView key() const { return KeyView{pos, bits, gems, beams, pos_stride, pos_agent_stride, beam_stride}; }
+};
+
+// Word w of the record in environment k: the identity words (w <= w_gems) from a KeyView, every word from a BatchView.
+LLE_SEARCH_HD uint32_t env_word(const KeyView& v, const RecordLayout& r, int64_t k, int w) {
+    if (w < r.n_pos) {
+        uint32_t x = 0u;
+        for (int b = 0; b < 4; b++) {
+            const int byte = 4 * w + b;
+            if (byte < 2 * r.A) x |= (uint32_t)v.pos[k * v.pos_stride + (byte >> 1) * v.pos_agent_stride + (byte & 1)] << (8 * b);
+        }
+        return x;
+    }
+    if (w == r.w_bits) return (uint32_t)v.bits[k];
+    if (w == r.w_bits + 1) return (uint32_t)(v.bits[k] >> 32);
+    if (w < r.w_gems) return v.beams[k * v.beam_stride + (w - r.w_beams)];
+    return v.gems[k];
+}
+LLE_SEARCH_HD uint32_t env_word(const BatchView& v, const RecordLayout& r, int64_t k, int w) {
+    if (w <= r.w_gems) return env_word(v.key(), r, k, w);
+    uint32_t x = 0u;
+    for (int b = 0; b < 4; b++) {
+        const int a = 4 * (w - r.w_avail) + b;
+        if (a < r.A) x |= (uint32_t)v.avail[k * v.avail_stride + a] << (8 * b);
+    }
+    return x;
+}
+struct EnvRecord {  // the record in environment k, as the functor hash_record and same_record read
+    const BatchView& v;
+    const RecordLayout& r;
+    int64_t k;
+    LLE_SEARCH_HD uint32_t operator()(int w) const { return env_word(v, r, k, w); }
+};
+// State s of a pool stored as structure of arrays: word w at base[w * stride + s] (a wavefront's reads of word w are as dense as its
+// state indices).  One pool: (pool, max_states).  A map's segment of the forest's: (pool + map * n_words * cap, cap).
+struct PoolRecord {
+    const uint32_t* base;
+    uint64_t stride, s;
+    LLE_SEARCH_HD uint32_t operator()(int w) const { return base[(uint64_t)w * stride + s]; }
+};
+
+// One work item: the record `rec` with the joint action `code` (base 5, agent 0 the lowest digit) into environment k -- state, mask
+// and action digits -- when every component is in the record's availability bytes.  Returns that; an unavailable item writes nothing.
+template <class Record>
+LLE_SEARCH_HD bool scatter_item(const BatchView& v, const RecordLayout& r, const Record& rec, int64_t k, uint32_t code) {
+    const uint32_t av[2] = {rec(r.w_avail), r.n_av > 1 ? rec(r.w_avail + 1) : 0u};
+    auto avail = [&](int a) { return (av[a >> 2] >> (8 * (a & 3))) & 255u; };
+    if (!joint_available(code, r.A, avail)) return false;
+    for (int w = 0; w < r.n_pos; w++) {
+        const uint32_t x = rec(w);
+        for (int b = 0; b < 4; b++) {
+            const int byte = 4 * w + b;
+            if (byte < 2 * r.A) v.pos[k * v.pos_stride + (byte >> 1) * v.pos_agent_stride + (byte & 1)] = (uint8_t)(x >> (8 * b));
+        }
+    }
+    v.bits[k] = (uint64_t)rec(r.w_bits) | (uint64_t)rec(r.w_bits + 1) << 32;
+    for (int w = 0; w < r.Lw; w++) v.beams[k * v.beam_stride + w] = rec(r.w_beams + w);
+    v.gems[k] = rec(r.w_gems);
+    for (int a = 0; a < r.A; a++) {
+        v.avail[k * v.avail_stride + a] = (uint8_t)avail(a);
+        v.actions[k * v.act_stride + a] = (uint8_t)(code % 5u);
+        code /= 5u;
+    }
+    return true;
+}
+
+// The record in environment k into state idx of a pool (base, stride as PoolRecord's).
+LLE_SEARCH_HD void copy_record(const BatchView& v, const RecordLayout& r, int64_t k, uint32_t* base, uint64_t stride, uint64_t idx) {
+    for (int w = 0; w < r.n_words; w++) base[(uint64_t)w * stride + idx] = env_word(v, r, k, w);
+}
+
+template <class A, class B>
+LLE_SEARCH_HD bool same_record(const A& a, const B& b, int n_key) {
+    for (int w = 0; w < n_key; w++)
+        if (a(w) != b(w)) return false;
+    return true;
+}
+
+// Whom the occupant of a table slot may name: tag t < n_tags the candidate in environment env0 + t of `batch`, whose record lies
+// complete there since the step; an index s < cap state s of the pool.  A finished table names states only: n_tags = 0.
+struct Occupants {
+    KeyView batch;
+    int64_t env0;
+    uint32_t n_tags;
+    const uint32_t* pool;
+    uint64_t stride, cap;
+};
+// Is `occupant` the record `me`, on its first r.n_key words?  (A tag or index out of range names nobody: no such occupant in a sound table.)
+template <class Record>
+LLE_SEARCH_HD bool occupant_is(const Occupants& o, const RecordLayout& r, uint32_t occupant, const Record& me) {
+    if (occupant & TAG_BIT) {
+        const uint32_t tag = occupant & ~TAG_BIT;
+        if (tag >= o.n_tags) return false;
+        const int64_t k = o.env0 + tag;
+        return same_record([&](int w) { return env_word(o.batch, r, k, w); }, me, r.n_key);
+    }
+    if (occupant >= o.cap) return false;
+    return same_record(PoolRecord{o.pool, o.stride, occupant}, me, r.n_key);
+}
+
+// bits_lo, gems: the words w_bits and w_gems of a record.  G = the map's gems.
+LLE_SEARCH_HD bool is_goal(uint32_t bits_lo, uint32_t gems, const RecordLayout& r, bool collect_gems, int G) {
+    return all_arrived(bits_lo, r.A) && (!collect_gems || all_gems(gems, G));
+}
+
+// Does an agent of the record `root` stand on a cell where a beam of another colour may run (foreign: H * W bytes, foreign_bit)?
+LLE_SEARCH_HD bool root_on_foreign_beam(const uint32_t* root, const RecordLayout& r, const uint8_t* foreign, int H, int W) {
+    for (int a = 0; a < r.A; a++) {
+        const uint32_t ij = root[a >> 1] >> (16 * (a & 1));
+        const int i = ij & 255u, j = (ij >> 8) & 255u;
+        if (i < H && j < W && on_foreign_beam(foreign[i * W + j], a)) return true;
+    }
+    return false;
 }
 
 }  // namespace lle_search_logic

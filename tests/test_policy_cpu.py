@@ -31,7 +31,10 @@ def test_library_exports():
     assert '#include "../../include/lle_policy.h"' in source and '#include "policy_logic.hpp"' in source
     assert '#include "../search/search_logic.hpp"' in logic
     assert "lle_batch_set_state" not in source and "capi_internal" not in source  # states move through the buffers of the public ABI only
-    assert "unsigned long long" not in source and "asm" not in source               # 32-bit global atomics, no inline assembly
+    shared = [open(os.path.join(ROOT, "lle_amd", "search", h)).read() for h in ("search_logic.hpp", "search_device.hpp")]
+    assert '#include "../search/search_device.hpp"' in source
+    for text in [source, logic] + shared:  # everything that compiles into the library: 32-bit global atomics, no inline assembly
+        assert "unsigned long long" not in text and "asm" not in text
     structs = {"lle_policy_options": policy.PolicyOptions, "lle_policy_args": policy.PolicyArgs, "lle_policy_result": policy.PolicyResult}
     fields = [(name, f) for name, cls in structs.items() for f, _ in cls._fields_]
     prints = "".join(f'printf("%zu ", sizeof({name}));' for name in structs)
@@ -53,8 +56,8 @@ def test_library_exports():
 
 def test_the_files_of_the_search_are_not_this_library_s():
     """policy.hip has its own kernels: the search's and the forest's sources do not know the library."""
-    for path in ("lle_amd/search/search.hip", "lle_amd/search/search_logic.hpp", "lle_amd/forest/forest.hip", "lle_amd/forest/forest_logic.hpp",
-                 "include/lle_search.h", "include/lle_forest.h"):
+    for path in ("lle_amd/search/search.hip", "lle_amd/search/search_logic.hpp", "lle_amd/search/search_device.hpp", "lle_amd/forest/forest.hip",
+                 "lle_amd/forest/forest_logic.hpp", "include/lle_search.h", "include/lle_forest.h"):
         assert "policy" not in open(os.path.join(ROOT, path)).read()
 
 

@@ -1,6 +1,7 @@
 """The solver without a GPU: header / exports / binding of liblle_search.so, the lower bound, every argument error and refusal, the solve
-modes, and the table code of lle_amd/search/search_logic.hpp under AddressSanitizer + UndefinedBehaviorSanitizer in a stand-alone
-program (tests/hostsim/search_table.cpp).  The search itself runs on the MI355X (tests/test_gpu_solver.py)."""
+modes, and the table code and the record I/O of lle_amd/search/search_logic.hpp under AddressSanitizer + UndefinedBehaviorSanitizer in
+stand-alone programs (tests/hostsim/search_table.cpp, tests/hostsim/record_io.cpp).  The search itself runs on the MI355X
+(tests/test_gpu_solver.py)."""
 import ctypes as C
 import importlib.util
 import os
@@ -216,3 +217,19 @@ def test_table_code_under_sanitizers(tmp_path):
         assert res.returncode == 0, f"rc={res.returncode}\n{res.stdout[-3000:]}\n{res.stderr[-6000:]}"
         out = dict(kv.split("=") for kv in res.stdout.split()[1:])
         assert res.stdout.startswith("OK ") and int(out["inserts"]) > 50000 and int(out["duplicates"]) > 10000 and int(out["full"]) >= 160
+
+
+def test_record_io_under_sanitizers(tmp_path):
+    """tests/hostsim/record_io.cpp: its own main over the record I/O of search_logic.hpp -- the code that search.hip, forest.hip and
+    policy.hip run between a batch, a pool and a table slot -- on fake batches in exactly sized vectors, built with
+    g++ -fsanitize=address,undefined and run as a child process; nothing sanitized is loaded into this interpreter."""
+    exe = str(tmp_path / "record_io")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(ROOT, "tests", "hostsim", "record_io.cpp"), "-o", exe] + SAN, check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    for seed in (1, 2):
+        res = subprocess.run([exe, str(seed)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=300)
+        assert res.returncode == 0, f"rc={res.returncode}\n{res.stdout[-3000:]}\n{res.stderr[-6000:]}"
+        out = dict(kv.split("=") for kv in res.stdout.split()[1:])
+        # 6 agent counts x 4 beam-word counts x 2 agent pitches x 2 key widths; all 5 + 25 + 125 codes below four agents, 203 above
+        assert res.stdout.startswith("OK ") and int(out["cases"]) == 96 and int(out["codes"]) == 16 * (5 + 25 + 125 + 3 * 203)
+        assert int(out["valid"]) > 500 and int(out["compared"]) > 2000
