@@ -10,7 +10,7 @@ call.  The graph queries are host Python over a few dozen edges, written from th
 
 `WorldCharacterizer` answers the solver-backed questions -- solvable within t_max, the shortest plan, is cooperation required -- with
 the exact shortest-plan search of lle_amd.solver (liblle_search.so) in place of the reference's SAT encoding; the predicates that
-need the other solve modes are out of scope.  Many worlds at once: `lle_amd.characterize_many` (lle_amd.forest), and the generator's
+need the other solve modes raise here, and `lle_amd.HelpGraphCharacterizer` (lle_amd.helpgraph) answers those over the help graph.  Many worlds at once: `lle_amd.characterize_many` (lle_amd.forest), and the generator's
 filter vocabulary over it in lle_amd.generator.  For whole batches use `BatchedLLE(..., cooperation=True)`.
 """
 from dataclasses import dataclass

@@ -326,9 +326,11 @@ class Constraint:
                 return False
         return bool(self.predicate.holds(c))
 
-    def is_satisfied_by(self, world, **solver_options):
-        """Whether `world` satisfies the constraint: one WorldCharacterizer (`solver_options` go to its Solver)."""
-        return self._accepts(WorldCharacterizer(world, self.t_max, **solver_options))
+    def is_satisfied_by(self, world, *, characterizer=WorldCharacterizer, **solver_options):
+        """Whether `world` satisfies the constraint: one `characterizer` (`solver_options` go to its Solver).  WorldCharacterizer
+        answers Solvable / Independent / Cooperative; lle_amd.HelpGraphCharacterizer also Asymmetric, Convergent, Divergent and
+        Interdependent(2)."""
+        return self._accepts(characterizer(world, self.t_max, **solver_options))
 
     def satisfied_by_many(self, worlds, **options):
         """A bool array, entry i == is_satisfied_by(worlds[i]), through `characterize_many`: the worlds are grouped by shape and

@@ -310,11 +310,15 @@ class Solver:
         rows = rows + [stay] * (length - len(rows))
         return [tuple(Action(v) for v in row) for row in rows]
 
+    def _check_mode(self, mode):
+        """The parsed solve mode when this solver serves it; NotImplementedError otherwise.  (Subclasses over other libraries replace it.)"""
+        return _native_mode(mode)
+
     # ---- the reference's interface
     def find_shortest(self, mode="standard", *, t_min=None, collect_gems=False, shuffle=False):
         """The shortest plan of at most t_max steps, padded with all-STAY rows up to `t_min`; None when there is none (or the padded
         plan would exceed t_max).  `shuffle` is accepted and has no effect (it randomises the SAT solver of the reference)."""
-        mode = _native_mode(mode)
+        mode = self._check_mode(mode)
         if t_min is None or t_min < self.solution_lower_bound:
             t_min = self.solution_lower_bound
         elif t_min > self.t_max:
@@ -334,7 +338,7 @@ class Solver:
             raise ValueError(f"path_length must be non-negative, got {path_length}.")
         elif path_length > self.t_max:
             raise ValueError(f"path_length={path_length} exceeds this solver's t_max={self.t_max}. Construct a new Solver with a larger t_max.")
-        mode = _native_mode(mode)
+        mode = self._check_mode(mode)
         if path_length < self.solution_lower_bound:
             return None
         rows = self._shortest(mode, collect_gems)
