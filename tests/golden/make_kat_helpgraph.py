@@ -10,6 +10,14 @@ reference; only inputs and expected outputs are kept.
 tests/helpgraph_ref.py existed, `frontier` and `expanded` per depth are what tests/helpgraph_ref.py gives (tests/test_helpgraph_cpu.py
 holds it to every entry here).  `maps` are the maps that are not the reference's.
 
+A search may carry a `changes` key: what is done to the world of the map text BEFORE the search is set up, as plain data --
+  {"sources": [{"laser_id": 0, "enabled": false, "colour": null}, ...], "exits": [[i, j], ...]}
+`sources`: per listed source, `enabled` switches it on or off and `colour` recolours it (null or missing: as the text has it);
+`exits`: the new exit cells, the old ones become floor (a cell under a beam may be given).  tests/helpgraph_ref.py applies it to the
+oracle world (set_source / set_exits before the reset) and to an lle_amd.World (LaserSource.disable / enable / set_colour, the
+exit_pos setter) before the solver is constructed, which keeps the map as it is at that moment.  A search without the key runs on the
+map as written.
+
 One layout of the catalogue has no search here: `fully-coupled-4agents` stores 84 128 records within its t_max of 8 (13 991 in the plain
 search of lle_amd.Solver), far beyond what the restatement walks in test time.  Both searches, which step through `World.step`, find NO
 plan within 8 steps on it, where the reference, whose solver is a SAT model of the rules, states `fully_coupled` for that horizon: the
@@ -128,12 +136,56 @@ L0E . . .  .
  .  . . L1W .
  X  . . X  .
 """,
+    # two sources of colour 0 (laser_id 0 on row 1, laser_id 1 on row 2) whose beams share no cell: agent 1 crosses both rows behind
+    # agent 0, so the plan's edge (0, 1) comes from either source; the gem lies under the first beam, off the shortest way
+    "shared-colour": """
+ @  S0 S1  .  @
+L0E .  .   G  @
+L0E .  .   .  @
+ @  X  X   @  @
+""",
+    # three beams of three colours run through (2, 2): L1S down column 2 (over the start of agent 1 and the exit (4, 2)), L0E and L2W
+    # along row 2 (over the gem).  World.lasers lists the outer two layers of a cell only, so at (2, 2) the source parsed first, L1S,
+    # owns no tile: there the cell's word holds two bits, not three.  Agents 0 and 2 have to enter row 2 in the same step, each
+    # blocking the beam that would kill the other, with agent 1 between them helped by both.
+    "three-beam-cell": """
+ @  S0 L1S S2  @
+ @  .  S1  .   @
+L0E .  .   G  L2W
+ @  .  .   .   @
+ @  X  X   X   @
+""",
+    # six agents whose edges lie in both help words: (3, 5) is bit 29 of the low word, (5, 3) bit 43 = bit 11 of the high word
+    "six-mutual": """
+ @  S5 S3  @  S0 S1 S2 S4
+L5E .  .   @  X  X  X  X
+ @  .  .  L3W @  @  @  @
+ @  X  X   @  @  @  @  @
+""",
+    # helpers 3 (low word) and 5 (high word) converge on agent 4
+    "six-converge": """
+ @  S3 S4 S5  @  S0 S1 S2
+L3E .  .  .   @  X  X  X
+ @  .  .  .  L5W @  @  @
+ @  X  X  X   @  @  @  @
+""",
 }
 
+# changes (see above)
+OFF0 = {"sources": [{"laser_id": 0, "enabled": False, "colour": None}]}
+OFF2 = {"sources": [{"laser_id": 2, "enabled": False, "colour": None}]}
+RECOLOURED = {"sources": [{"laser_id": 0, "enabled": None, "colour": 1}]}
+ALL_OFF = {"sources": [{"laser_id": l, "enabled": False, "colour": None} for l in range(3)]}  # nobody can help anybody: every mode is `standard`
+EXITS_SINGLE = {"exits": [[1, 1], [2, 2]]}   # single-laser-asymmetric: the exit (1, 1) lies under the beam, next to the source
+EXITS_COMPACT = {"exits": [[3, 0], [2, 2]]}  # two-agent-mutual-compact: the exit (2, 2) lies under the beam of L1W
 
-def S(map_name, t_max, mode, length, states, param=2, collect_gems=False, frontier=None, expanded=None):
-    return dict(map=map_name, t_max=t_max, mode=mode, param=param, collect_gems=collect_gems, length=length, states=states, frontier=frontier,
-                expanded=expanded)
+
+def S(map_name, t_max, mode, length, states, param=2, collect_gems=False, frontier=None, expanded=None, changes=None):
+    out = dict(map=map_name, t_max=t_max, mode=mode, param=param, collect_gems=collect_gems, length=length, states=states, frontier=frontier,
+               expanded=expanded)
+    if changes is not None:
+        out["changes"] = changes
+    return out
 
 
 SEARCHES = [
@@ -174,6 +226,41 @@ SEARCHES = [
     S("paper-fully-coupled-legacy", 10, "no-convergence", 6, 4375, param=3, frontier=[1, 9, 64, 301, 809, 1608, 1583], expanded=[18, 353, 2889, 13316, 34557, 57096]),
     S("paper-fully-coupled-legacy", 10, "no-divergence", None, 930, frontier=[1, 8, 50, 184, 252, 247, 118, 58, 11, 1, 0], expanded=[18, 317, 2231, 7160, 8657, 6811, 2929, 1460, 129, 6]),
     S("paper-fully-coupled-legacy", 10, "no-divergence", 6, 4375, param=3, frontier=[1, 9, 64, 301, 809, 1608, 1583], expanded=[18, 353, 2889, 13316, 34557, 57096]),
+    # ---- maps of this project's making and changed worlds, all worked out with tests/helpgraph_ref.py
+    S("shared-colour", 6, "standard", 3, 49, frontier=[1, 4, 14, 30], expanded=[6, 49, 172]),
+    S("shared-colour", 6, "no-asymmetric", None, 76, frontier=[1, 4, 14, 30, 21, 5, 1], expanded=[6, 49, 172, 288, 147, 26]),
+    S("shared-colour", 6, "standard", 5, 123, collect_gems=True, frontier=[1, 4, 14, 37, 42, 25], expanded=[6, 49, 172, 375, 359]),
+    S("three-beam-cell", 5, "standard", 4, 169, frontier=[1, 7, 2, 22, 137], expanded=[16, 90, 91, 1037]),
+    S("three-beam-cell", 5, "no-mutual", None, 8, frontier=[1, 7, 0], expanded=[16, 90]),
+    S("three-beam-cell", 5, "no-convergence", None, 75, frontier=[1, 7, 1, 12, 42, 12], expanded=[16, 90, 64, 536, 654]),
+    S("three-beam-cell", 5, "no-divergence", None, 131, frontier=[1, 7, 1, 12, 50, 60], expanded=[16, 90, 64, 536, 960]),
+    S("three-beam-cell", 5, "no-convergence", 4, 169, param=3, frontier=[1, 7, 2, 22, 137], expanded=[16, 90, 91, 1037]),
+    # source 2 (L2W) disabled: agent 1 may stand on (2, 2) with agent 0 alone at its side
+    S("three-beam-cell", 5, "standard", 4, 347, changes=OFF2, frontier=[1, 7, 8, 66, 265], expanded=[16, 90, 275, 2791]),
+    S("three-beam-cell", 5, "no-asymmetric", None, 692, changes=OFF2, frontier=[1, 7, 8, 66, 265, 345], expanded=[16, 90, 275, 2791, 5918]),
+    S("three-beam-cell", 5, "no-convergence", 4, 334, changes=OFF2, frontier=[1, 7, 8, 66, 252], expanded=[16, 90, 275, 2791]),
+    # source 0 disabled / recoloured to 1 / an exit moved under a beam
+    S("single-laser-asymmetric", 6, "standard", 2, 17, changes=OFF0, frontier=[1, 3, 13], expanded=[4, 33]),
+    S("single-laser-asymmetric", 6, "no-asymmetric", 2, 17, changes=OFF0, frontier=[1, 3, 13], expanded=[4, 33]),
+    S("single-laser-asymmetric", 6, "standard", 4, 17, changes=RECOLOURED, frontier=[1, 1, 5, 4, 6], expanded=[4, 12, 30, 19]),
+    S("single-laser-asymmetric", 6, "no-asymmetric", None, 26, changes=RECOLOURED, frontier=[1, 1, 5, 4, 6, 6, 3], expanded=[4, 12, 30, 19, 27, 33]),
+    S("single-laser-asymmetric", 6, "standard", 2, 6, changes=EXITS_SINGLE, frontier=[1, 2, 3], expanded=[4, 6]),
+    S("single-laser-asymmetric", 6, "no-asymmetric", None, 7, changes=EXITS_SINGLE, frontier=[1, 2, 3, 1, 0], expanded=[4, 6, 6, 2]),
+    S("two-agent-mutual-compact", 6, "standard", 5, 130, changes=OFF0, frontier=[1, 5, 10, 17, 36, 61], expanded=[6, 47, 115, 208, 461]),
+    S("two-agent-mutual-compact", 6, "no-asymmetric", None, 205, changes=OFF0, frontier=[1, 5, 10, 17, 36, 61, 75], expanded=[6, 47, 115, 208, 461, 655]),
+    S("two-agent-mutual-compact", 6, "no-mutual", 5, 130, changes=OFF0, frontier=[1, 5, 10, 17, 36, 61], expanded=[6, 47, 115, 208, 461]),
+    S("two-agent-mutual-compact", 6, "standard", 5, 64, changes=EXITS_COMPACT, frontier=[1, 3, 6, 13, 22, 19], expanded=[6, 29, 61, 140, 167]),
+    S("two-agent-mutual-compact", 6, "no-mutual", None, 58, changes=EXITS_COMPACT, frontier=[1, 3, 6, 12, 19, 15, 2], expanded=[6, 29, 61, 136, 156, 107]),
+    S("paper-fully-coupled", 10, "standard", 7, 6346, changes=ALL_OFF, frontier=[1, 7, 73, 424, 1126, 1719, 1801, 1195], expanded=[8, 256, 3205, 20958, 55497, 77509, 62527]),
+    # six agents at t_max 3, the shortest horizon at which 'no plan' says something: edges in both help words
+    S("six-mutual", 3, "standard", 3, 1920, frontier=[1, 47, 436, 1436], expanded=[64, 3561, 29933]),
+    S("six-mutual", 3, "no-mutual", None, 1536, frontier=[1, 47, 392, 1096], expanded=[64, 3561, 26972]),
+    S("six-converge", 3, "standard", 3, 4880, frontier=[1, 39, 728, 4112], expanded=[64, 6296, 110470]),
+    S("six-converge", 3, "no-mutual", None, 3300, frontier=[1, 39, 648, 2612], expanded=[64, 6296, 92900]),
+    S("six-converge", 3, "no-convergence", None, 4220, frontier=[1, 39, 680, 3500], expanded=[64, 6296, 102700]),
+    S("six-converge", 3, "no-divergence", None, 2420, frontier=[1, 31, 544, 1844], expanded=[64, 5216, 78650]),
+    S("six-converge", 3, "no-divergence", 3, 4880, param=3, frontier=[1, 39, 728, 4112], expanded=[64, 6296, 110470]),
+    S("six-converge", 3, "no-fully-coupled", 3, 4880, frontier=[1, 39, 728, 4112], expanded=[64, 6296, 110470]),
 ]
 
 

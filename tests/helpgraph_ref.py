@@ -16,7 +16,13 @@ The modes, as the reference's predicates define them on a flattened relation E (
                      states that do not count are stored like any other (they are absorbing)
 A level is always finished before the search stops on a goal, so `frontier` and `expanded` by depth are reproducible.
 
-Results are cached per (map, t_max, mode, param, collect_gems): the CPU and the GPU tests share one computation.
+Results are cached per (map, changes, t_max, mode, param, collect_gems): the CPU and the GPU tests share one computation.
+
+`changes` (optional everywhere; None: the map as its text gives it) is plain data, as tests/golden/kat_helpgraph.json stores it:
+  {"sources": [{"laser_id": 0, "enabled": false, "colour": null}, ...], "exits": [[i, j], ...]}
+Either key may be missing; `enabled` / `colour` null or missing: left as the text has it.  It is applied to the fresh OracleWorld with
+set_source / set_exits before the reset (`oracle_world`), and to an lle_amd.World through LaserSource.disable() / enable() /
+set_colour() and the exit_pos setter (`apply_changes`) before a solver is constructed over it.
 """
 import itertools
 import json
@@ -74,19 +80,82 @@ def accepts(edges, mode):
     return all(h in helped for h, _b in edges)
 
 
+def changes_key(changes):
+    """`changes` as a hashable value: equal data, equal key."""
+    return None if changes is None else json.dumps(changes, sort_keys=True)
+
+
+def oracle_world(text, changes=None):
+    """A fresh OracleWorld of the map text with `changes` applied; not reset yet."""
+    world = oracle.OracleWorld(text)
+    if changes is not None:
+        assert set(changes) <= {"sources", "exits"}, sorted(changes)
+        for src in changes.get("sources", ()):
+            assert set(src) <= {"laser_id", "enabled", "colour"} and 0 <= src["laser_id"] < world.n_sources, src
+            world.set_source(src["laser_id"], enabled=src.get("enabled"), colour=src.get("colour"))
+        if "exits" in changes:
+            world.set_exits(changes["exits"])
+    return world
+
+
+def apply_changes(world, changes=None):
+    """The same data on an lle_amd.World, through its public mutators; returns the world.  Call it before the solver is constructed: a
+    solver keeps the map as it is at construction."""
+    if changes is not None:
+        assert set(changes) <= {"sources", "exits"}, sorted(changes)
+        sources = {s.laser_id: s for s in world.laser_sources}
+        for src in changes.get("sources", ()):
+            handle = sources[src["laser_id"]]
+            if src.get("enabled") is not None:
+                handle.enable() if src["enabled"] else handle.disable()
+            if src.get("colour") is not None:
+                handle.set_colour(src["colour"])
+        if "exits" in changes:
+            world.exit_pos = [tuple(p) for p in changes["exits"]]
+    return world
+
+
+def changes_label(changes):
+    """A short name of `changes` for test ids: "" for None, else e.g. "-source0-off", "-source0-colour1", "-exits-1.1-2.2"."""
+    if changes is None:
+        return ""
+    parts = []
+    for src in changes.get("sources", ()):
+        parts += [f"source{src['laser_id']}" + ("" if src.get("enabled") is None else "-on" if src["enabled"] else "-off")
+                  + ("" if src.get("colour") is None else f"-colour{src['colour']}")]
+    if "exits" in changes:
+        parts.append("exits-" + "-".join(f"{i}.{j}" for i, j in changes["exits"]))
+    return "-" + "-".join(parts)
+
+
+def n_agents_of(text):
+    """The number of agents of a map text: its distinct start tokens S<k>."""
+    return len({tok for tok in text.split() if tok[0] == "S" and tok[1:].isdigit()})
+
+
+def embed(text, height, width):
+    """The map `text` in the bottom-right corner of a height x width map that is wall everywhere else: the same world (walls on every
+    side of a map change nothing), every cell it uses at the far end of the cell table and of the position bytes."""
+    rows = [line.split() for line in text.strip().splitlines()]
+    h, w = len(rows), len(rows[0])
+    assert all(len(r) == w for r in rows) and h <= height and w <= width
+    return "\n".join(" ".join(rows[i - (height - h)][j - (width - w)] if i >= height - h and j >= width - w else "@" for j in range(width))
+                     for i in range(height))
+
+
 _CACHE = {}
 
 
-def search(text, t_max, mode="standard", param=2, collect_gems=False):
-    key = (text, int(t_max), mode, int(param), bool(collect_gems))
+def search(text, t_max, mode="standard", param=2, collect_gems=False, changes=None):
+    key = (text, changes_key(changes), int(t_max), mode, int(param), bool(collect_gems))
     if key not in _CACHE:
-        _CACHE[key] = _search(text, int(t_max), mode, int(param), bool(collect_gems))
+        _CACHE[key] = _search(text, int(t_max), mode, int(param), bool(collect_gems), changes)
     return _CACHE[key]
 
 
-def _search(text, t_max, mode, param, collect_gems):
+def _search(text, t_max, mode, param, collect_gems, changes=None):
     assert mode in MODES
-    world = oracle.OracleWorld(text)
+    world = oracle_world(text, changes)
     A = world.n_agents
     world.reset()
     res = Result(None, None, [1], [])
@@ -128,9 +197,9 @@ def _search(text, t_max, mode, param, collect_gems):
     return res
 
 
-def replay_edges(text, plan):
+def replay_edges(text, plan, changes=None):
     """The flattened help relation of `plan` on a fresh oracle world; asserts that nobody dies.  Returns (edges, world)."""
-    world = oracle.OracleWorld(text)
+    world = oracle_world(text, changes)
     world.reset()
     assert all(world.alive())
     edges = set(coop_ref.detect(world))
@@ -142,12 +211,12 @@ def replay_edges(text, plan):
     return edges, world
 
 
-def check_plan(text, plan, mode="standard", param=2, collect_gems=False, length=None):
+def check_plan(text, plan, mode="standard", param=2, collect_gems=False, length=None, changes=None):
     """Replay `plan` (rows of action values) on a fresh oracle world: nobody dies, everybody arrives, and the flattened edges of the
     replay satisfy the mode.  Returns the edges."""
     if length is not None:
         assert len(plan) == length, (len(plan), length)
-    edges, world = replay_edges(text, plan)
+    edges, world = replay_edges(text, plan, changes)
     assert all(world.arrived()), "not every agent has arrived"
     if collect_gems:
         assert all(world.gems_collected())
@@ -157,14 +226,14 @@ def check_plan(text, plan, mode="standard", param=2, collect_gems=False, length=
 
 
 # ---------------------------------------------------------------------------------------------- the reference's predicates
-def characterize(text, t_max):
+def characterize(text, t_max, changes=None):
     """The reference's WorldCharacterizer questions (world_characterization.py) answered with this search: what the golden file states."""
     n_agents = oracle.OracleWorld(text).n_agents
-    standard = search(text, t_max)
+    standard = search(text, t_max, changes=changes)
     solvable = standard.length is not None
 
     def none(mode, k=2):
-        return search(text, t_max, mode, k).length is None
+        return search(text, t_max, mode, k, changes=changes).length is None
 
     def asymmetric():
         # (is_asymmetric also asks for a laser colour and for no independent plan: a plan that avoids every edge avoids the asymmetric ones,

@@ -20,7 +20,7 @@ CONFIGS = {"defaults": {}, "chunk64": dict(chunk=64, max_states=16384)}
 
 
 def search_id(s):
-    return f"{s['map']}-t{s['t_max']}-{s['mode']}-{s['param']}" + ("-gems" if s["collect_gems"] else "")
+    return f"{s['map']}-t{s['t_max']}-{s['mode']}-{s['param']}" + ("-gems" if s["collect_gems"] else "") + helpgraph_ref.changes_label(s.get("changes"))
 
 
 def mode_text(mode, param=2):
@@ -39,8 +39,12 @@ def values(plan):
     return None if plan is None else [[a.value for a in row] for row in plan]
 
 
-def run(hg, text, t_max, mode="standard", param=2, collect_gems=False, **options):
-    """(plan as rows of action values or None, last_stats) of one fresh HelpGraphSolver."""
+def run(hg, text, t_max, mode="standard", param=2, collect_gems=False, changes=None, **options):
+    """(plan as rows of action values or None, last_stats) of one fresh HelpGraphSolver, over a World that `changes` was applied to
+    (tests/helpgraph_ref.py: apply_changes) when there are any."""
+    if changes is not None:
+        from lle_amd import World
+        text = helpgraph_ref.apply_changes(World(text), changes)
     s = hg.HelpGraphSolver(text, t_max, **options)
     try:
         plan = values(s.find_shortest(mode_text(mode, param), collect_gems=collect_gems))
@@ -50,9 +54,10 @@ def run(hg, text, t_max, mode="standard", param=2, collect_gems=False, **options
 
 
 def assert_recorded(hg, s, text=None, **options):
-    """One search of the golden file: length, counters and state count equal the restatement's; the plan replays on the oracle under the mode."""
-    text = MAPS[s["map"]] if text is None else text
-    plan, stats = run(hg, text, s["t_max"], s["mode"], s["param"], s["collect_gems"], **options)
+    """One search of the golden file: length, counters and state count equal the restatement's; the plan replays on the oracle under the mode
+    (and under the entry's `changes`, if it has any)."""
+    text, changes = MAPS[s["map"]] if text is None else text, s.get("changes")
+    plan, stats = run(hg, text, s["t_max"], s["mode"], s["param"], s["collect_gems"], changes, **options)
     print(f"{search_id(s)} {options}: length {stats['length']} (ref {s['length']}), states {stats['n_states']} (ref {s['states']}), frontier {stats['frontier']}, "
           f"expanded {stats['expanded']}")
     assert stats["length"] == s["length"] and (plan is None) == (s["length"] is None)
@@ -60,14 +65,14 @@ def assert_recorded(hg, s, text=None, **options):
     if plan is None:
         assert stats["help_edges"] is None
     else:
-        edges = helpgraph_ref.check_plan(text, plan, s["mode"], s["param"], s["collect_gems"], length=s["length"])
+        edges = helpgraph_ref.check_plan(text, plan, s["mode"], s["param"], s["collect_gems"], length=s["length"], changes=changes)
         assert stats["help_edges"] == edges, "the goal's help words are the flattened edges of the plan's replay"
     return plan, stats
 
 
-# (the six-agent map has 15 625 joint actions per state: in pieces of 64 no piece ever holds two states, at half a million launches;
-# test_six_agents_reach_the_second_help_word runs it with the default chunk and with 4 096)
-LISTED = [s for s in SEARCHES if s["map"] != "six-agents"]
+# (a six-agent map has 15 625 joint actions per state: in pieces of 64 no piece ever holds two states, at half a million launches;
+# test_six_agents_reach_the_second_help_word and tests/test_gpu_helpgraph_maps.py run them with the default chunk and with 4 096)
+LISTED = [s for s in SEARCHES if helpgraph_ref.n_agents_of(MAPS[s["map"]]) < 6]
 
 
 @pytest.mark.parametrize("config", sorted(CONFIGS))

@@ -27,7 +27,7 @@ LAYOUTS = ["single-laser-asymmetric", "double-disjoint-asymmetric", "convergent-
 
 
 def search_id(s):
-    return f"{s['map']}-t{s['t_max']}-{s['mode']}-{s['param']}" + ("-gems" if s["collect_gems"] else "")
+    return f"{s['map']}-t{s['t_max']}-{s['mode']}-{s['param']}" + ("-gems" if s["collect_gems"] else "") + helpgraph_ref.changes_label(s.get("changes"))
 
 
 def test_kat_file_is_what_the_maker_writes():
@@ -48,6 +48,13 @@ def test_kat_file_is_what_the_maker_writes():
     for s in CASES["searches"]:
         assert s["map"] in MAPS and s["mode"] in helpgraph_ref.MODES and sum(s["frontier"]) == s["states"] <= 7599
         assert len(s["expanded"]) == len(s["frontier"]) - 1 and (s["length"] is None or s["length"] == len(s["expanded"]))
+    # what the restatement walks: no search added later expands more items than the largest of the first 37
+    ids = [search_id(s) for s in CASES["searches"]]
+    assert len(set(ids)) == len(ids) == 68
+    largest = max(CASES["searches"][:37], key=lambda s: sum(s["expanded"]))
+    assert search_id(largest) == "paper-fully-coupled-legacy-t10-no-fully-coupled-2" and sum(largest["expanded"]) == 247075
+    assert all(sum(s["expanded"]) <= 247075 for s in CASES["searches"])
+    assert all("changes" not in s for s in CASES["searches"][:37])
 
 
 def test_library_exports():
@@ -204,11 +211,167 @@ def test_the_restatement_reproduces_the_reference(text, t_max, key, k, want):
 
 @pytest.mark.parametrize("s", CASES["searches"], ids=[search_id(s) for s in CASES["searches"]])
 def test_the_restatement_reproduces_the_recorded_searches(s):
-    res = helpgraph_ref.search(MAPS[s["map"]], s["t_max"], s["mode"], s["param"], s["collect_gems"])
+    changes = s.get("changes")
+    res = helpgraph_ref.search(MAPS[s["map"]], s["t_max"], s["mode"], s["param"], s["collect_gems"], changes=changes)
     assert (res.length, res.n_states, res.frontier, res.expanded) == (s["length"], s["states"], s["frontier"], s["expanded"])
     if res.plan is not None:
-        edges = helpgraph_ref.check_plan(MAPS[s["map"]], res.plan, s["mode"], s["param"], s["collect_gems"], length=s["length"])
+        edges = helpgraph_ref.check_plan(MAPS[s["map"]], res.plan, s["mode"], s["param"], s["collect_gems"], length=s["length"], changes=changes)
         assert edges == res.edges
+
+
+# ------------------------------------------------------------------------------------------------ changed worlds
+def recorded(map_name, mode="standard", param=2, collect_gems=False, changes=None):
+    return next(s for s in CASES["searches"] if (s["map"], s["mode"], s["param"], s["collect_gems"], s.get("changes")) == (map_name, mode, param, collect_gems, changes))
+
+
+OFF0 = {"sources": [{"laser_id": 0, "enabled": False, "colour": None}]}
+RECOLOURED = {"sources": [{"laser_id": 0, "enabled": None, "colour": 1}]}
+
+
+def test_changes_reach_the_oracle_world_and_the_cache_key():
+    """`changes` is applied before the reset and is part of the cache key; None is the map as written.  The figures are the ones the
+    hook was specified with, worked out independently of it: on single-laser-asymmetric at t_max 6, source 0 disabled: `standard` finds
+    length 2 with 17 records and no edges, `no-asymmetric` length 2 (no plan on the map as written); source 0 recoloured to 1:
+    `standard` finds length 4 with the edge (1, 0), `no-asymmetric` no plan with 26 records."""
+    text = MAPS["single-laser-asymmetric"]
+    plain = helpgraph_ref.search(text, 6)
+    assert helpgraph_ref.search(text, 6, changes=None) is plain and (plain.length, plain.n_states, plain.edges) == (2, 14, {(0, 1)})
+    off = helpgraph_ref.search(text, 6, changes=OFF0)
+    assert off is not plain and off is helpgraph_ref.search(text, 6, changes={"sources": [{"colour": None, "enabled": False, "laser_id": 0}]})
+    assert (off.length, off.n_states, off.edges) == (2, 17, set())
+    assert helpgraph_ref.search(text, 6, "no-asymmetric").length is None and helpgraph_ref.search(text, 6, "no-asymmetric", changes=OFF0).length == 2
+    red = helpgraph_ref.search(text, 6, changes=RECOLOURED)
+    assert (red.length, red.edges) == (4, {(1, 0)})
+    none = helpgraph_ref.search(text, 6, "no-asymmetric", changes=RECOLOURED)
+    assert (none.length, none.n_states) == (None, 26)
+    assert helpgraph_ref.check_plan(text, red.plan, changes=RECOLOURED) == {(1, 0)}
+    with pytest.raises(Exception):  # the plan of the recoloured world kills agent 0 on the map as written
+        helpgraph_ref.check_plan(text, red.plan)
+    w = helpgraph_ref.oracle_world(text, {"exits": [[1, 1], [2, 2]]})
+    assert sorted(w.exit_pos) == [(1, 1), (2, 2)] and (1, 1) in {(i, j) for i, j, *_ in w.lasers()}  # an exit under the beam
+    answers = helpgraph_ref.characterize(text, 6, changes=OFF0)
+    assert answers["solvable"] and not answers["asymmetric"]() and helpgraph_ref.characterize(text, 6)["asymmetric"]()
+    assert [helpgraph_ref.changes_label(c) for c in (None, OFF0, RECOLOURED, {"exits": [[1, 1], [2, 2]]})] == ["", "-source0-off", "-source0-colour1", "-exits-1.1-2.2"]
+
+
+def test_changes_reach_a_world_of_the_package():
+    """`apply_changes` does to an lle_amd.World, through its public mutators, what `oracle_world` does to the oracle's: the sources and
+    the exits of the two agree afterwards (no device: a World parses on the host)."""
+    for name, changes in (("single-laser-asymmetric", OFF0), ("single-laser-asymmetric", RECOLOURED), ("two-agent-mutual-compact", {"exits": [[3, 0], [2, 2]]}),
+                          ("three-beam-cell", {"sources": [{"laser_id": 2, "enabled": False, "colour": None}, {"laser_id": 0, "colour": 1}], "exits": [[4, 1], [4, 3], [3, 2]]}),
+                          ("paper-fully-coupled", None)):
+        ours, theirs = helpgraph_ref.apply_changes(World(MAPS[name]), changes), helpgraph_ref.oracle_world(MAPS[name], changes)
+        assert [(s.laser_id, s.agent_id, s.is_enabled) for s in ours.laser_sources] == [(l, src[3], bool(src[4])) for l, src in enumerate(theirs.sources())]
+        assert sorted(ours.exit_pos) == sorted(theirs.exit_pos)
+    w = helpgraph_ref.apply_changes(World(MAPS["single-laser-asymmetric"]), OFF0)
+    assert [s.is_enabled for s in w.laser_sources] == [False] and [s.is_enabled for s in World(MAPS["single-laser-asymmetric"]).laser_sources] == [True]
+    assert helpgraph_ref.apply_changes(w, {"sources": [{"laser_id": 0, "enabled": True}]}).laser_sources[0].is_enabled
+
+
+# ------------------------------------------------------------------------------------------------ the maps of this project's making
+NEW_MAPS = ("shared-colour", "three-beam-cell", "six-mutual", "six-converge")
+
+
+def edges_by_source(text, plan, changes=None):
+    """{laser_id: the (helper, beneficiary) pairs that source gives over the states of `plan`}, the rule of tests/coop_ref.py per source."""
+    world = helpgraph_ref.oracle_world(text, changes)
+    world.reset()
+    out = {}
+    for joint in [None] + list(plan):
+        if joint is not None:
+            world.step([int(a) for a in joint])
+        on_beam = {}
+        for i, j, laser_id, colour, _on, enabled in world.lasers():
+            if enabled and world.tile_agent(i, j) >= 0:
+                on_beam.setdefault((laser_id, colour), set()).add(world.tile_agent(i, j))
+        for (laser_id, colour), agents in on_beam.items():
+            if colour in agents and len(agents) > 1:
+                out.setdefault(laser_id, set()).update((colour, b) for b in agents if b != colour)
+    return out
+
+
+@pytest.mark.parametrize("name", NEW_MAPS)
+def test_a_new_map_discriminates(name):
+    """Some recorded mode of the map differs from `standard` in length or frontier, and every new map is not one of the reference's."""
+    mine = [s for s in CASES["searches"] if s["map"] == name and "changes" not in s and not s["collect_gems"]]
+    standard = next(s for s in mine if s["mode"] == "standard")
+    assert name in CASES["maps"] and standard["length"] is not None
+    assert any((s["length"], s["frontier"]) != (standard["length"], standard["frontier"]) for s in mine)
+
+
+def test_shared_colour_has_two_sources_of_one_colour():
+    """Two laser_ids of colour 0 whose beams share no cell; the plan's edges come from the second source (and from the first: a rule that
+    kept only one source per colour loses edges whichever it keeps)."""
+    text = MAPS["shared-colour"]
+    world = helpgraph_ref.oracle_world(text)
+    assert [(src[3], bool(src[4])) for src in world.sources()] == [(0, True), (0, True)]
+    cells = [{(i, j) for i, j, laser_id, *_ in world.lasers() if laser_id == l} for l in (0, 1)]
+    assert cells[0] and cells[1] and not cells[0] & cells[1]
+    res = helpgraph_ref.search(text, 6)
+    assert edges_by_source(text, res.plan) == {0: {(0, 1)}, 1: {(0, 1)}} and res.edges == {(0, 1)}
+    # without the second source's edges the plan would be independent of agent 0 from step 2 on: the beam is what agent 1 has to cross
+    assert helpgraph_ref.search(text, 6, changes={"sources": [{"laser_id": 1, "enabled": False}]}).length == 3
+    gems = helpgraph_ref.search(text, 6, collect_gems=True)
+    assert (res.length, gems.length) == (3, 5) and (1, 3) in world.gem_pos and (1, 3) in cells[0]  # the gem lies under a beam, off the way
+
+
+def test_three_beam_cell_has_three_beams_and_two_owners():
+    """Three sources of three colours shine through (2, 2).  `World.lasers` -- the oracle's, the reference's and the package's -- lists
+    the outer two layers of a cell and no more, so NO cell ever carries three laser ids there: the first source parsed, L1S, owns no
+    tile at the crossing, and a cell word with three bits would be wrong.  The recorded plan has agent 1 on the crossing, helped along
+    both listed beams; one beam lies over a start and an exit, two over the gem."""
+    text = MAPS["three-beam-cell"]
+    world = helpgraph_ref.oracle_world(text)
+    step = {0: (-1, 0), 1: (0, 1), 2: (1, 0), 3: (0, -1)}  # Direction: N, E, S, W
+    through = {}
+    for l, (i, j, direction, colour, _enabled, length) in enumerate(world.sources()):
+        for k in range(1, length + 1):
+            through.setdefault((i + k * step[direction][0], j + k * step[direction][1]), []).append((l, colour))
+    assert sorted(through[(2, 2)]) == [(0, 1), (1, 0), (2, 2)] and max(len(v) for v in through.values()) == 3
+    listed = {}
+    for i, j, laser_id, *_ in world.lasers():
+        listed.setdefault((i, j), []).append(laser_id)
+    assert listed[(2, 2)] == [2, 1] and max(len(v) for v in listed.values()) == 2  # outermost first; the two-layer rule
+    assert {c for c, v in listed.items() if 0 in v} == {(1, 2), (3, 2), (4, 2)} and (1, 2) == tuple(world.start_pos[1]) and (4, 2) in world.exit_pos
+    assert listed[(2, 3)] == [2, 1] and (2, 3) in world.gem_pos
+    res = helpgraph_ref.search(text, 5)
+    assert res.length == 4 and res.edges == {(0, 1), (0, 2), (2, 0), (2, 1)}
+    world.reset()
+    for joint in res.plan[:2]:
+        world.step(joint)
+    assert world.positions() == [(2, 1), (2, 2), (2, 3)]  # three agents on the two beams through the crossing, agent 1 on it
+    assert edges_by_source(text, res.plan) == {1: {(0, 1), (0, 2)}, 2: {(2, 1), (2, 0)}}
+    # with L2W disabled agent 1 stands on the crossing with agent 2 below it on L1S's beam -- and helps nobody from there
+    off2 = {"sources": [{"laser_id": 2, "enabled": False, "colour": None}]}
+    world = helpgraph_ref.oracle_world(text, off2)
+    world.reset()
+    for joint in ([1, 4, 1], [1, 4, 1], [4, 4, 1], [4, 1, 3]):
+        world.step(joint)
+    assert world.positions() == [(2, 1), (2, 2), (3, 2)] and all(world.alive())
+    from tests import coop_ref
+    assert coop_ref.detect(world) == {(0, 1)}
+
+
+def test_six_agent_maps_use_both_help_words():
+    for name, edges in (("six-mutual", {(3, 5), (5, 3)}), ("six-converge", {(3, 4), (3, 5), (5, 3), (5, 4)})):
+        res = helpgraph_ref.search(MAPS[name], 3)
+        bits = {8 * h + b for h, b in res.edges}
+        assert res.edges == edges and min(bits) < 32 <= max(bits)
+    assert {s["mode"] for s in CASES["searches"] if s["map"] == "six-mutual" and s["length"] is None} == {"no-mutual"}
+    assert {(s["mode"], s["param"]) for s in CASES["searches"] if s["map"] == "six-converge" and s["length"] is None} == {("no-mutual", 2), ("no-convergence", 2), ("no-divergence", 2)}
+    assert {(s["mode"], s["param"]) for s in CASES["searches"] if s["map"] == "six-converge" and s["length"] == 3} == {("standard", 2), ("no-divergence", 3), ("no-fully-coupled", 2)}
+
+
+def test_a_map_in_the_far_corner_is_the_same_world():
+    """`embed` puts a layout in the bottom-right corner of a map of walls: the restatement gives the small layout's recorded counters,
+    so what tests/test_gpu_helpgraph_maps.py finds on the device with such a map is the device's."""
+    s = recorded("two-agent-mutual-compact")
+    for height, width in ((20, 20), (6, 255)):
+        big = helpgraph_ref.embed(MAPS[s["map"]], height, width)
+        world = helpgraph_ref.oracle_world(big)
+        assert (world.height, world.width) == (height, width) and min(i * width + j for i, j, *_ in world.lasers()) > 255
+        res = helpgraph_ref.search(big, s["t_max"])
+        assert (res.length, res.frontier, res.expanded) == (s["length"], s["frontier"], s["expanded"])
 
 
 def test_check_plan_refuses_what_a_mode_rejects():
