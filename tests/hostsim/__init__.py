@@ -131,8 +131,10 @@ class SimBatch:
         assert n >= 0, "malformed packed image"
         return (a[:n] if has.value else None), b[:n]
 
-    def reset(self):
-        self.L.hs_reset(self.h, None)
+    def reset(self, env_mask=None):
+        """World.reset for every env, or for those with env_mask != 0 (uint8 [n])."""
+        mask = None if env_mask is None else np.ascontiguousarray(env_mask, dtype=np.uint8)
+        self.L.hs_reset(self.h, None if mask is None else mask.ctypes.data)
 
     def step(self, actions=None, flags=0, seed=0, t=0, env_offset=0):
         ap = None

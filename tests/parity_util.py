@@ -49,6 +49,13 @@ def assert_state_equal(eng, dump, where=""):
             raise AssertionError(f"{where}: '{key}' differs in {len(set(bad[:, 0]))} envs; first env {e}: engine={a[e].tolist()} oracle={b[e].tolist()}")
 
 
+def assert_set_state_events(eng, rec, where):
+    """evcount / events of the set_state itself against the events the oracle's set_state returned, in order."""
+    for key in ("ev_count", "events"):
+        bad = np.nonzero((eng[key] != rec[key]).reshape(len(eng[key]), -1).any(1))[0]
+        assert not len(bad), f"{where}: '{key}' differs in {len(bad)} envs; first env {bad[0]}: engine={eng[key][bad[0]].tolist()} oracle={rec[key][bad[0]].tolist()}"
+
+
 def assert_step_equal(eng, ostep, where="", check_obs=True):
     """ostep: dict returned by OracleBatch.step()."""
     n, cap = eng["events"].shape[0], eng["events"].shape[1]

@@ -363,12 +363,14 @@ def joint_actions(rng, masks, parity):
     return acts
 
 
-def apply_states(oracle_mod, ob, case, lo=0, rng=None):
-    """set_state on every world of `ob` (the envs [lo, lo + ob.n) of `case`).  With `rng` (worlds that carry their own source colours
+def apply_states(oracle_mod, ob, case, lo=0, rng=None, record=None):
+    """set_state on every world of `ob` (the envs [lo, lo + ob.n) of `case`); `record`, a dict, receives the events the oracle
+    returned (ev_count [n], events [n, 2 A, 2], rows beyond the count zero).  With `rng` (worlds that carry their own source colours
     and flags) a request the env's world refuses is replaced, in `case`, by a fresh draw that it accepts and a joint action drawn from
     its masks.  Returns ghost [n, A]: dead without a death event, which LLE's `done` does not count (env.py:208-217)."""
     n, A = ob.n, case.A
     ghost = np.zeros((n, A), bool)
+    ev_count, events = np.zeros(n, np.uint8), np.zeros((n, 2 * A, 2), np.uint8)
     geo = None
     for e in range(n):
         w = ob.world(e)
@@ -394,6 +396,11 @@ def apply_states(oracle_mod, ob, case, lo=0, rng=None):
             case.actions[k] = [[q for q in range(5) if (m >> q) & 1][int(rng.integers(bin(m & 31).count("1")))] for m in masks]
         died = {a for (ty, a) in ev if ty == EV_DIED}
         ghost[e] = [not case.alive[k][a] and a not in died for a in range(A)]
+        ev_count[e] = len(ev)
+        if ev:
+            events[e, :len(ev)] = ev
+    if record is not None:
+        record["ev_count"], record["events"] = ev_count, events
     return ghost
 
 
@@ -491,13 +498,13 @@ def structural_classes(name, A):
     return out
 
 
-def run_oracle(oracle_mod, case, sources=None, rng=None):
+def run_oracle(oracle_mod, case, sources=None, rng=None, record=None):
     """An oracle batch with the case's states applied: (ob, ghost, dump after set_state).  `sources(ob)` may re-colour / switch the
-    worlds' sources first (then `rng` replaces what an env's world refuses)."""
+    worlds' sources first (then `rng` replaces what an env's world refuses); `record`: see apply_states."""
     ob = oracle_mod.OracleBatch(case.text, case.n)
     if sources is not None:
         sources(ob)
-    ghost = apply_states(oracle_mod, ob, case, 0, rng)
+    ghost = apply_states(oracle_mod, ob, case, 0, rng, record)
     return ob, ghost, ob.dump()
 
 
@@ -589,14 +596,15 @@ FOLLOW_UPS = [(1, False), (2, False), (3, True)]   # (t, auto_reset) of the samp
 
 class Reference:
     """The oracle's side of the protocol, computed once per case: `after_set_state` and `steps[k]` are records with
-    dump / done / ghost (+ ostep / reward for steps, + whatever `extras(ob)` returned)."""
+    dump / done / ghost (+ the events set_state returned, + ostep / reward for steps, + whatever `extras(ob)` returned)."""
 
 
 def reference_run(oracle_mod, case, sources=None, rng=None, env_offset=ENV_OFFSET, extras=None, follow_ups=None):
     ref = Reference()
-    ob, ghost, d0 = run_oracle(oracle_mod, case, sources, rng)
+    returned = {}
+    ob, ghost, d0 = run_oracle(oracle_mod, case, sources, rng, returned)
     ref.ob, ref.case = ob, case
-    ref.after_set_state = {"dump": d0, "ghost": ghost.copy(), "done": done_of(d0, ghost), "extras": extras(ob) if extras else None,
+    ref.after_set_state = {"dump": d0, "ev_count": returned["ev_count"], "events": returned["events"], "ghost": ghost.copy(), "done": done_of(d0, ghost), "extras": extras(ob) if extras else None,
                            "obs": np.stack([ob.world(e).obs() for e in range(case.n)])}
     ref.steps = []
     plan = [(0, False, case.actions)] + [(t, auto, None) for t, auto in (FOLLOW_UPS if follow_ups is None else follow_ups)]

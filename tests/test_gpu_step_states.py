@@ -27,7 +27,7 @@ import pytest
 
 from tests import instantiation_maps as im
 from tests import step_states as ss
-from tests.parity_util import assert_state_equal, assert_step_equal, legal_colours, unpack_engine
+from tests.parity_util import assert_set_state_events, assert_state_equal, assert_step_equal, legal_colours, unpack_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -125,6 +125,7 @@ def _check_set_state(bw, refs, tag):
         eng, bufs = _engine(bw, ref, lo)
         rec = ref.after_set_state
         assert_state_equal(eng, rec["dump"], f"{tag} after set_state, block {m}")
+        assert_set_state_events(eng, rec, f"{tag} after set_state, block {m}")
         assert np.array_equal(eng["obs"], rec["obs"]), f"{tag}: observation after set_state, block {m}"
         assert np.array_equal(bufs["done"], rec["done"]), f"{tag}: done after set_state, block {m}"
         lo += ref.case.n

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tests import step_states as ss
-from tests.parity_util import assert_state_equal, assert_step_equal, legal_colours, unpack_engine
+from tests.parity_util import assert_set_state_events, assert_state_equal, assert_step_equal, legal_colours, unpack_engine
 
 ENGINES = ["env", "lanes", "lanes_no_shortcut"]
 PER_ENV_MAPS = ["q1", "nested", "four_layers", "long_crossing", "im_7_7x", "many_agents"]
@@ -43,6 +43,7 @@ def _run_protocol(sb, ref, tag, env_offset=ss.ENV_OFFSET):
     assert not sb.buf("err").any(), f"{tag}: set_state refused envs {np.nonzero(sb.buf('err'))[0][:8].tolist()} the oracle accepts"
     eng = unpack_engine(_bufs(sb), *ob.dims)
     assert_state_equal(eng, ref.after_set_state["dump"], f"{tag} after set_state")
+    assert_set_state_events(eng, ref.after_set_state, f"{tag} after set_state")
     assert np.array_equal(sb.buf("done"), ref.after_set_state["done"]), f"{tag}: done after set_state"
     assert np.array_equal(eng["obs"], ref.after_set_state["obs"]), f"{tag}: observation after set_state"
     stats0 = sb.buf("stats").copy()
