@@ -1,7 +1,7 @@
 """The full cooperation profile of one world: which shapes of cooperation EVERY plan within t_max must show.
 
-`HelpGraphCharacterizer` answers with exact searches on the GPU (liblle_search.so, liblle_helpgraph.so): a shape is required when
-the world is solvable and no plan within t_max avoids it.  The world is `paper-fully-coupled` of the reference's layouts catalogue
+`TrailCharacterizer` answers with exact searches on the GPU (liblle_search.so, liblle_helpgraph.so, and liblle_trails.so for
+`is_sequential`): a shape is required when the world is solvable and no plan within t_max avoids it.  The world is `paper-fully-coupled` of the reference's layouts catalogue
 (python/tests/world_layouts.py): three agents, three lasers, and no way out in which somebody is not helped by everybody else.
 
     python examples/characterize_world.py [t_max]
@@ -22,11 +22,11 @@ S2   .   . . . @
 
 
 def main():
-    from lle_amd import HelpGraphCharacterizer, World
+    from lle_amd import TrailCharacterizer, World
     from lle_amd.characterization import profile_plan
     t_max = int(sys.argv[1]) if len(sys.argv) > 1 else 10
     world = World(PAPER_FULLY_COUPLED)
-    c = HelpGraphCharacterizer(world, t_max)
+    c = TrailCharacterizer(world, t_max)  # a HelpGraphCharacterizer that answers is_sequential as well
     plan = c.shortest_path
     print(f"t_max = {t_max}: shortest plan {None if plan is None else len(plan)} steps, shortest independent plan "
           f"{None if c.shortest_independent_path is None else len(c.shortest_independent_path)}")
@@ -36,12 +36,15 @@ def main():
     rows = [("solvable", c.is_solvable()), ("cooperative", c.is_cooperative()), ("independent", c.is_independent()), ("asymmetric", c.is_asymmetric()),
             ("mutual", c.is_mutual()), ("fully coupled", c.is_fully_coupled())]
     rows += [(f"convergent({k})", c.is_convergent(k)) for k in (2, 3)] + [(f"divergent({k})", c.is_divergent(k)) for k in (2, 3)]
+    rows += [(f"sequential({n})", c.is_sequential(n)) for n in (2, 3, 4)]
     for name, value in rows:
         print(f"  {name:<16}{value}")
     for name, path in (("non-asymmetric", c.shortest_non_asymmetric_path), ("non-fully-coupled", c.shortest_non_fully_coupled_path),
                        ("without mutual help", c.compute_shortest_non_interdependent_path(2)), ("without 2-convergence", c.compute_shortest_path_without_convergence(2)),
-                       ("without 2-divergence", c.compute_shortest_path_without_divergence(2))):
-        print(f"  shortest plan {name:<22}{'none' if path is None else len(path)}")
+                       ("without 2-divergence", c.compute_shortest_path_without_divergence(2)),
+                       ("without a sequence of 2", c.compute_shortest_path_without_sequence(2)),
+                       ("without a sequence of 3", c.compute_shortest_path_without_sequence(3))):
+        print(f"  shortest plan {name:<26}{'none' if path is None else len(path)}")
     c._solver.free()
 
 

@@ -33,6 +33,9 @@ def __getattr__(name):
     if name in ("HelpGraphSolver", "HelpGraphCharacterizer"):  # (the solve modes over the help graph, liblle_helpgraph.so)
         from . import helpgraph
         return getattr(helpgraph, name)
+    if name in ("TrailSolver", "TrailCharacterizer"):  # (no-sequence-N: trails of help events in time order, liblle_trails.so)
+        from . import trails
+        return getattr(trails, name)
     if name in ("ForestSolver", "ForestResult", "solve_many", "characterize_many"):  # (the same search over many maps at once, liblle_forest.so)
         from . import forest
         return getattr(forest, name)
@@ -54,4 +57,4 @@ __all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorl
            "InvalidWorldStateError", "Laser", "LaserSource", "LaserSubgoal", "Layered", "LayeredPadded", "Map", "MapParseError", "MultiGenerator", "MultiObjective", "NoExtras",
            "ObservationType", "ParsingError", "PartialGenerator", "PotentialShapedLLE", "SingleObjective", "SolveMode", "Solver", "SolverCapacityError", "StateGenerator", "World", "WorldCharacterizer", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "solve", "types", "world",
            "ForestSolver", "ForestResult", "solve_many", "characterize_many", "Constraint", "WorldFilter", "generate_n",
-           "OptimalPolicy", "PolicyCapacityError", "HelpGraphSolver", "HelpGraphCharacterizer"]
+           "OptimalPolicy", "PolicyCapacityError", "HelpGraphSolver", "HelpGraphCharacterizer", "TrailSolver", "TrailCharacterizer"]

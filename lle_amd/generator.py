@@ -141,7 +141,7 @@ class Asymmetric(Predicate):
 
 @dataclass(frozen=True)
 class Sequential(Predicate):
-    """A chain of at least `length` help edges is required (solve mode 'no-sequence-N': not built)."""
+    """A chain of at least `length` help edges is required (solve mode 'no-sequence-N': answered by lle_amd.TrailCharacterizer)."""
     length: int = 2
 
     def __post_init__(self):
@@ -329,7 +329,7 @@ class Constraint:
     def is_satisfied_by(self, world, *, characterizer=WorldCharacterizer, **solver_options):
         """Whether `world` satisfies the constraint: one `characterizer` (`solver_options` go to its Solver).  WorldCharacterizer
         answers Solvable / Independent / Cooperative; lle_amd.HelpGraphCharacterizer also Asymmetric, Convergent, Divergent and
-        Interdependent(2)."""
+        Interdependent(2); lle_amd.TrailCharacterizer also Sequential(N)."""
         return self._accepts(characterizer(world, self.t_max, **solver_options))
 
     def satisfied_by_many(self, worlds, **options):
