@@ -4,7 +4,7 @@
 filtered by one `Constraint.satisfied_by_many`: two forest runs (lle_amd/liblle_forest.so) that walk the search trees of all its
 candidates in the same launches -- any plan, and a plan in which nobody stands in somebody else's beam.
 """
-from lle_amd import Constraint, Cooperative, Solvable, characterize_many, generate_n, mapgen, solve_many
+from lle_amd import Asymmetric, Constraint, Cooperative, Sequential, Solvable, TrailCharacterizer, characterize_many, generate_n, mapgen, solve_many
 
 keep = Constraint(t_max=12, predicate=Cooperative(), min_solution_length=4)
 worlds = list(generate_n(8, keep, height=5, width=5, n_agents=2, n_lasers=2, n_gems=1, n_exits=2, wall_fraction=0.12, seed=0, batch=128, max_attempts=2048))
@@ -24,3 +24,9 @@ for k, (world, plan) in enumerate(zip(worlds, plans)):
 easy = Constraint(12, Solvable() & ~Cooperative())
 candidates = [mapgen.generate(5, 5, 2, 2, 1, n_exits=2, wall_fraction=0.12, n_voids=0, seed=s) for s in range(64)]
 print("of the first 64 candidates,", int(easy.satisfied_by_many(candidates).sum()), "can be solved without cooperation")
+
+# worlds that REQUIRE a shape of cooperation: the help forest (lle_amd/liblle_helpforest.so) answers the atoms over the help graph
+lopsided = Constraint(12, Asymmetric() & ~Sequential(3))
+worlds = list(generate_n(4, lopsided, characterizer=TrailCharacterizer, height=5, width=5, n_agents=2, n_lasers=2, n_exits=2, wall_fraction=0.12, seed=0,
+                         batch=128, max_attempts=1024))
+print(f"{len(worlds)} worlds in which somebody must help without being helped, and no chain of three help events is needed")

@@ -39,6 +39,9 @@ def __getattr__(name):
     if name in ("ForestSolver", "ForestResult", "solve_many", "characterize_many"):  # (the same search over many maps at once, liblle_forest.so)
         from . import forest
         return getattr(forest, name)
+    if name in ("HelpForestSolver", "HelpForestResult", "ManyHelpCharacterization"):  # (the help-graph and trail modes over many maps, liblle_helpforest.so)
+        from . import helpforest
+        return getattr(helpforest, name)
     if name in ("Predicate", "Solvable", "Independent", "Cooperative", "Asymmetric", "Sequential", "Convergent", "Divergent", "Interdependent", "And", "Or",
                 "Not", "WorldRequirements", "Constraint", "WorldFilter", "generate_n"):  # (lle.generator: the filter vocabulary)
         from . import generator
@@ -57,4 +60,5 @@ __all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorl
            "InvalidWorldStateError", "Laser", "LaserSource", "LaserSubgoal", "Layered", "LayeredPadded", "Map", "MapParseError", "MultiGenerator", "MultiObjective", "NoExtras",
            "ObservationType", "ParsingError", "PartialGenerator", "PotentialShapedLLE", "SingleObjective", "SolveMode", "Solver", "SolverCapacityError", "StateGenerator", "World", "WorldCharacterizer", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "solve", "types", "world",
            "ForestSolver", "ForestResult", "solve_many", "characterize_many", "Constraint", "WorldFilter", "generate_n",
-           "OptimalPolicy", "PolicyCapacityError", "HelpGraphSolver", "HelpGraphCharacterizer", "TrailSolver", "TrailCharacterizer"]
+           "OptimalPolicy", "PolicyCapacityError", "HelpGraphSolver", "HelpGraphCharacterizer", "TrailSolver", "TrailCharacterizer",
+           "HelpForestSolver", "HelpForestResult", "ManyHelpCharacterization"]

@@ -2,13 +2,14 @@
 generator on top of `lle_amd.mapgen`.
 
 A `Predicate` is a value object describing a property of a world at a horizon: the atoms `Solvable`, `Independent`, `Cooperative`
-(and the atoms of the solve modes the search does not build: `Asymmetric`, `Sequential`, `Convergent`, `Divergent`,
-`Interdependent`), combined with `&`, `|`, `~` into `And`, `Or`, `Not`.  A `Constraint` adds the horizon `t_max` and an optional
+(and the atoms of the solve modes over the help graph, which need a `characterizer`: `Asymmetric`, `Sequential`, `Convergent`,
+`Divergent`, `Interdependent`), combined with `&`, `|`, `~` into `And`, `Or`, `Not`.  A `Constraint` adds the horizon `t_max` and an optional
 minimum length of the shortest plan:
 
-    keep = Constraint(10, Cooperative() & ~Sequential(3), min_solution_length=4)   # evaluating Sequential raises NotImplementedError
+    keep = Constraint(10, Cooperative() & ~Sequential(3), min_solution_length=4)   # Sequential needs a TrailCharacterizer
     Constraint(10, Cooperative()).is_satisfied_by(world)           # one WorldCharacterizer: two searches of one map
     Constraint(10, Cooperative()).satisfied_by_many(worlds)        # a bool array: two forest runs per shape (lle_amd.forest)
+    keep.satisfied_by_many(worlds, characterizer=TrailCharacterizer)   # the help forest (lle_amd.helpforest): a run per atom and shape
     worlds = list(generate_n(100, Constraint(12, Cooperative()), height=5, width=5, n_agents=2, n_lasers=2))
 
 `satisfied_by_many` is new here: the reference filters its candidates one at a time.  Of the reference's generator only the filter
@@ -125,7 +126,8 @@ class Cooperative(Predicate):
 
 @dataclass(frozen=True)
 class Asymmetric(Predicate):
-    """Needs the solve mode 'no-asymmetric': evaluating raises the characterizer's NotImplementedError."""
+    """Some help edge's helper is never helped, in every plan (solve mode 'no-asymmetric': answered by lle_amd.HelpGraphCharacterizer and
+    lle_amd.TrailCharacterizer; pass either as `characterizer=` to `satisfied_by_many` / `generate_n` and the help forest answers)."""
 
     def holds(self, c):
         return c.is_asymmetric()
@@ -141,7 +143,8 @@ class Asymmetric(Predicate):
 
 @dataclass(frozen=True)
 class Sequential(Predicate):
-    """A chain of at least `length` help edges is required (solve mode 'no-sequence-N': answered by lle_amd.TrailCharacterizer)."""
+    """A chain of at least `length` help edges is required (solve mode 'no-sequence-N': answered by lle_amd.TrailCharacterizer; pass it as
+    `characterizer=` to `satisfied_by_many` / `generate_n` and the help forest answers)."""
     length: int = 2
 
     def __post_init__(self):
@@ -162,7 +165,8 @@ class Sequential(Predicate):
 
 @dataclass(frozen=True)
 class Convergent(Predicate):
-    """One agent must be helped by `k` distinct agents (solve mode 'no-convergence-N': not built)."""
+    """One agent must be helped by `k` distinct agents (solve mode 'no-convergence-N': answered by lle_amd.HelpGraphCharacterizer and
+    lle_amd.TrailCharacterizer; pass either as `characterizer=` to `satisfied_by_many` / `generate_n` and the help forest answers)."""
     k: int
 
     def __post_init__(self):
@@ -183,7 +187,8 @@ class Convergent(Predicate):
 
 @dataclass(frozen=True)
 class Divergent(Predicate):
-    """One agent must help `k` distinct agents (solve mode 'no-divergence-N': not built)."""
+    """One agent must help `k` distinct agents (solve mode 'no-divergence-N': answered by lle_amd.HelpGraphCharacterizer and
+    lle_amd.TrailCharacterizer; pass either as `characterizer=` to `satisfied_by_many` / `generate_n` and the help forest answers)."""
     k: int = 2
 
     def __post_init__(self):
@@ -204,7 +209,8 @@ class Divergent(Predicate):
 
 @dataclass(frozen=True)
 class Interdependent(Predicate):
-    """A closed chain of help over `order` agents is required (solve mode 'no-interdependence-N': not built)."""
+    """A closed chain of help over `order` agents is required (solve mode 'no-interdependence-N': order 2 is 'no-mutual', answered like
+    `Asymmetric`; N >= 3 is not built)."""
     order: int = 2
 
     def __post_init__(self):
@@ -332,13 +338,26 @@ class Constraint:
         Interdependent(2); lle_amd.TrailCharacterizer also Sequential(N)."""
         return self._accepts(characterizer(world, self.t_max, **solver_options))
 
-    def satisfied_by_many(self, worlds, **options):
-        """A bool array, entry i == is_satisfied_by(worlds[i]), through `characterize_many`: the worlds are grouped by shape and
-        every group is searched as one forest (`options`: envs_per_map, max_states_per_map, device)."""
-        from .forest import characterize_many
+    def satisfied_by_many(self, worlds, *, characterizer=None, **options):
+        """A bool array, entry i == is_satisfied_by(worlds[i], characterizer=characterizer), searched together: the worlds are grouped
+        by shape and every group is one forest (`options`: envs_per_map, max_states_per_map, device).  `characterizer` None: the
+        plain forest (`lle_amd.forest.characterize_many`), which answers Solvable / Independent / Cooperative.
+        lle_amd.HelpGraphCharacterizer or lle_amd.TrailCharacterizer: the help forest (`lle_amd.helpforest.characterize_many`),
+        which also answers Asymmetric, Convergent, Divergent, Interdependent(2) and -- under TrailCharacterizer -- Sequential(N); every
+        atom costs at most one forest run per shape, made when the first world needs it.  Any other class: one such characterizer
+        per world (then `options` go to its Solver)."""
         worlds = list(worlds)
-        many = characterize_many(worlds, self.t_max, **options)
-        return np.array([self._accepts(_Answered(many, i)) for i in range(len(worlds))], dtype=bool)
+        if characterizer is None:
+            from .forest import characterize_many
+            many = characterize_many(worlds, self.t_max, **options)
+            return np.array([self._accepts(_Answered(many, i)) for i in range(len(worlds))], dtype=bool)
+        from .helpgraph import HelpGraphCharacterizer
+        from .trails import TrailCharacterizer
+        if characterizer in (HelpGraphCharacterizer, TrailCharacterizer):
+            from . import helpforest
+            with helpforest.characterize_many(worlds, self.t_max, sequential=characterizer is TrailCharacterizer, **options) as many:
+                return np.array([self._accepts(many.entry(i)) for i in range(len(worlds))], dtype=bool)
+        return np.array([self.is_satisfied_by(w, characterizer=characterizer, **options) for w in worlds], dtype=bool)
 
 
 WorldFilter = Constraint  # the reference's earlier name
@@ -348,7 +367,9 @@ def generate_n(n, constraint, *, height, width, n_agents, n_lasers=0, n_gems=0, 
                max_attempts=None, **options):
     """Yield up to `n` Worlds that satisfy `constraint`, in candidate order: candidate i is
     `mapgen.generate(height, width, n_agents, n_lasers, n_gems, n_exits, wall_fraction, n_voids, seed=seed + i)` for i = 0, 1, ...;
-    candidates are drawn `batch` at a time and every batch is filtered by one `constraint.satisfied_by_many` (`options` go there).  The
+    candidates are drawn `batch` at a time and every batch is filtered by one `constraint.satisfied_by_many` (`options` go there:
+    envs_per_map, max_states_per_map, device -- and `characterizer=lle_amd.TrailCharacterizer` or `lle_amd.HelpGraphCharacterizer`
+    for constraints over Asymmetric, Sequential, Convergent, Divergent or Interdependent(2), which the help forest then answers).  The
     worlds that come out depend on the arguments only, not on `batch`.  Stops after `n` accepted worlds or `max_attempts` candidates
     (None: no limit -- a constraint nothing satisfies then never ends).
 
