@@ -7,7 +7,7 @@ search in Python.
 
 Per set and "mode/param" a list with one entry per map: `length` (null: no plan within the set's t_max), `frontier` and `expanded` per
 depth and `states` (distinct records stored), from `helpgraph_ref.search` (modes over the flattened help relation) or
-`trails_ref.search` (no-sequence-N), with the set's collect_gems.  Nothing is trimmed: every set has the maps, the t_max and the
+`trails_ref.search` (no-sequence-N), with the set's collect_gems and the map's `changes` (sets L and C).  Nothing is trimmed: every set has the maps, the t_max and the
 shape tests/helpforest_ref.py states.
 """
 import json
@@ -24,8 +24,8 @@ def record(s):
     out = {}
     for mode, param in s.modes:
         rows = []
-        for text in s.maps:
-            r = helpforest_ref.search(text, s.t_max, mode, param, s.collect_gems)
+        for text, changes in zip(s.maps, s.changes):
+            r = helpforest_ref.search(text, s.t_max, mode, param, s.collect_gems, changes=changes)
             rows.append(dict(length=r.length, frontier=list(r.frontier), expanded=list(r.expanded), states=r.n_states))
         out[helpforest_ref.golden_key(mode, param)] = rows
     return out

@@ -7,7 +7,9 @@ inputs and expected outputs are kept.
 
 `maps` are the maps that are not in the catalogue: five of tests/golden/kat_helpgraph.json, repeated here so that this file stands
 alone (`two-agent-mutual-compact` is the reference's, `three-beam-cell`, `gem-detour`, `six-mutual` and `six-converge` this
-project's), and three made for the trail search:
+project's), and four made for the trail search:
+  long-trails         two-agent-mutual-compact without reachable exits: no plan under any N, trails up to 15 edges, a frontier that
+                      runs empty at depth N + 5
   chain-in-one-state  agent 1 has to stand on the crossing of L0E and its own L1S while agent 2 crosses L1S below it: 0 -> 1 and 1 -> 2
                       in ONE state, a trail of two edges from one layer
   chain-at-reset      the same crossing with everybody standing there at the start: the reset state (t = 0) holds the trail already,
@@ -18,7 +20,9 @@ project's), and three made for the trail search:
 
 `searches` are the searches the GPU tests run, one per (map, t_max, n, collect_gems): `length` (null: no plan), `states` (distinct
 (world state, trail lengths) records stored), `frontier` and `expanded` per depth, all worked out with tests/trails_ref.py
-(tests/test_trails_cpu.py holds it to every entry here).
+(tests/test_trails_cpu.py holds it to every entry here).  A search may carry a `changes` key: what is done to the world of the map text
+BEFORE the search is set up, as plain data in the form of tests/golden/kat_helpgraph.json (tests/helpgraph_ref.py: `oracle_world`,
+`apply_changes`) -- {"sources": [{"laser_id": l, "enabled": false | true | null, "colour": c | null}, ...]}.
 
 What the searches find against what the reference states -- every stated value is reproduced by tests/trails_ref.py (where it
 finishes in test time) and by liblle_trails.so, with no contradiction.  Left out of the GPU comparison, by name:
@@ -209,11 +213,29 @@ L0E  S0  S1   @
 L0E  S0  .    @
  @   X   X    @
 """,
+    # two-agent-mutual-compact with its exits walled off (nobody ever arrives) and two exits nobody can reach: the agents can hold the
+    # mutual pair over STAYs for as long as N allows, so the trails grow to N - 1 <= 15 and every N in 2 .. 16 gives other counters
+    "long-trails": """
+ S0 . . S1  @ X
+L0E . . .   @ X
+ .  . . L1W @ @
+ .  . . .   @ @
+""",
 }
 
 
-def S(map_name, t_max, n, length, states, frontier, expanded, collect_gems=False):
-    return dict(map=map_name, t_max=t_max, n=n, collect_gems=collect_gems, length=length, states=states, frontier=frontier, expanded=expanded)
+def S(map_name, t_max, n, length, states, frontier, expanded, collect_gems=False, changes=None):
+    out = dict(map=map_name, t_max=t_max, n=n, collect_gems=collect_gems, length=length, states=states, frontier=frontier, expanded=expanded)
+    if changes is not None:
+        out["changes"] = changes
+    return out
+
+
+# changes (see above)
+OFF0 = {"sources": [{"laser_id": 0, "enabled": False, "colour": None}]}
+OFF1 = {"sources": [{"laser_id": 1, "enabled": False, "colour": None}]}
+RECOLOUR1 = {"sources": [{"laser_id": 1, "enabled": None, "colour": 0}]}
+ALL_OFF = {"sources": [{"laser_id": 0, "enabled": False, "colour": None}, {"laser_id": 1, "enabled": False, "colour": None}]}
 
 
 SEARCHES = [
@@ -247,6 +269,34 @@ SEARCHES = [
     S("six-mutual", 3, 2, None, 1536, [1, 47, 392, 1096], [64, 3561, 26972]),
     S("six-mutual", 3, 3, 3, 1856, [1, 47, 436, 1372], [64, 3561, 29933]),
     S("six-converge", 3, 3, 3, 4540, [1, 39, 728, 3772], [64, 6296, 110470]),
+    # long-trails: no plan for any N; the mutual pair is held over STAYs until some trail has N edges, so the search stores 100 + 76 (N - 2)
+    # records, its greatest stored field is N - 1 (up to 15) and its frontier runs empty at depth N + 5
+    S("long-trails", 24, 2, None, 100, [1, 3, 6, 12, 29, 40, 9, 0], [6, 29, 61, 160, 345, 404, 84]),
+    S("long-trails", 24, 3, None, 176, [1, 3, 6, 13, 34, 62, 46, 11, 0], [6, 29, 61, 172, 414, 705, 465, 102]),
+    S("long-trails", 24, 4, None, 252, [1, 3, 6, 13, 35, 67, 68, 48, 11, 0], [6, 29, 61, 172, 426, 774, 766, 483, 102]),
+    S("long-trails", 24, 5, None, 328, [1, 3, 6, 13, 35, 68, 73, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 835, 784, 483, 102]),
+    S("long-trails", 24, 6, None, 404, [1, 3, 6, 13, 35, 68, 74, 75, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 847, 853, 784, 483, 102]),
+    S("long-trails", 24, 7, None, 480, [1, 3, 6, 13, 35, 68, 74, 76, 75, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 847, 865, 853, 784, 483, 102]),
+    S("long-trails", 24, 8, None, 556, [1, 3, 6, 13, 35, 68, 74, 76, 76, 75, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 847, 865, 865, 853, 784, 483, 102]),
+    S("long-trails", 24, 9, None, 632, [1, 3, 6, 13, 35, 68, 74, 76, 76, 76, 75, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 847, 865, 865, 865, 853, 784, 483, 102]),
+    S("long-trails", 24, 10, None, 708, [1, 3, 6, 13, 35, 68, 74, 76, 76, 76, 76, 75, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 847, 865, 865, 865, 865, 853, 784, 483, 102]),
+    S("long-trails", 24, 11, None, 784, [1, 3, 6, 13, 35, 68, 74, 76, 76, 76, 76, 76, 75, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 847, 865, 865, 865, 865, 865, 853, 784, 483, 102]),
+    S("long-trails", 24, 12, None, 860, [1, 3, 6, 13, 35, 68, 74, 76, 76, 76, 76, 76, 76, 75, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 847, 865, 865, 865, 865, 865, 865, 853, 784, 483, 102]),
+    S("long-trails", 24, 13, None, 936, [1, 3, 6, 13, 35, 68, 74, 76, 76, 76, 76, 76, 76, 76, 75, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 847, 865, 865, 865, 865, 865, 865, 865, 853, 784, 483, 102]),
+    S("long-trails", 24, 14, None, 1012, [1, 3, 6, 13, 35, 68, 74, 76, 76, 76, 76, 76, 76, 76, 76, 75, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 847, 865, 865, 865, 865, 865, 865, 865, 865, 853, 784, 483, 102]),
+    S("long-trails", 24, 15, None, 1088, [1, 3, 6, 13, 35, 68, 74, 76, 76, 76, 76, 76, 76, 76, 76, 76, 75, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 847, 865, 865, 865, 865, 865, 865, 865, 865, 865, 853, 784, 483, 102]),
+    S("long-trails", 24, 16, None, 1164, [1, 3, 6, 13, 35, 68, 74, 76, 76, 76, 76, 76, 76, 76, 76, 76, 76, 75, 70, 48, 11, 0], [6, 29, 61, 172, 426, 786, 847, 865, 865, 865, 865, 865, 865, 865, 865, 865, 865, 853, 784, 483, 102]),
+    # changed worlds: one layout, four worlds, four answers under no-sequence-2 (unchanged: None / 100 above, at t_max 6 and 8 alike)
+    S("two-agent-mutual-compact", 8, 2, 5, 164, [1, 3, 6, 18, 57, 79], [6, 29, 61, 262, 708], changes=OFF1),
+    S("two-agent-mutual-compact", 8, 3, 5, 164, [1, 3, 6, 18, 57, 79], [6, 29, 61, 262, 708], changes=OFF1),
+    S("two-agent-mutual-compact", 8, 2, 5, 130, [1, 5, 10, 17, 36, 61], [6, 47, 115, 208, 461], changes=OFF0),
+    S("two-agent-mutual-compact", 8, 3, 5, 130, [1, 5, 10, 17, 36, 61], [6, 47, 115, 208, 461], changes=OFF0),
+    S("two-agent-mutual-compact", 8, 2, None, 107, [1, 3, 6, 15, 39, 33, 10, 0], [6, 29, 61, 218, 440, 263, 35], changes=RECOLOUR1),
+    S("two-agent-mutual-compact", 8, 3, None, 107, [1, 3, 6, 15, 39, 33, 10, 0], [6, 29, 61, 218, 440, 263, 35], changes=RECOLOUR1),
+    S("long-trails", 24, 16, None, 198, [1, 3, 6, 18, 57, 79, 31, 3, 0], [6, 29, 61, 262, 708, 823, 259, 15], changes=OFF1),
+    # every source disabled: nobody helps anybody, every N walks the plain search
+    S("two-agent-mutual-compact", 8, 2, 5, 151, [1, 5, 10, 22, 57, 56], [6, 47, 115, 303, 718], changes=ALL_OFF),
+    S("two-agent-mutual-compact", 8, 16, 5, 151, [1, 5, 10, 22, 57, 56], [6, 47, 115, 303, 718], changes=ALL_OFF),
 ]
 
 

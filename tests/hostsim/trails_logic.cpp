@@ -5,7 +5,8 @@
 //     random graphs of 2 .. 6 agents: every field of L while no trail has N edges, and REACHED at the first state at which one has
 //   * the known answers of tests/golden/kat_coop.json's longest_trail cases, which the test hands over as a text file (argv[2]): one case
 //     per line, "expected n_edges  h b t  h b t ..."
-//   * saturation: a mutual pair held state after state under N = 16 (fields never pass 15, REACHED in the eighth state) and N = 2
+//   * saturation: a mutual pair held state after state under N = 16 (fields never pass 15, REACHED in the eighth state) and N = 2;
+//     fixed cases with fields of 8 .. 15: the boundary between N = 15 and N = 16, the clamp of a trail of 16 in the first and the last field
 //   * the budget: a complete digraph on 6 agents with L = 0 and N = 16, and one on 4 agents (12 arcs, no trail of 16), either answer
 //     what the brute force gives or report dense -- never a wrong answer; a state of at most 6 arcs is never dense
 //   * the table code of search_logic.hpp with the trail word in the identity, the way tr_insert and tr_commit use it: candidates that
@@ -191,6 +192,25 @@ int main(int argc, char** argv) {
             CHECK(budget >= 0 && tl::field(L, 0) <= 15u && tl::field(L, 1) <= 15u && (L & 0x7FFFFF00u) == 0u);
             if (state < 8) CHECK(L == (uint32_t)(2 * state) * 0x11u && !tl::violates_sequence(L, 16, 2));
             else CHECK((L & tl::REACHED) != 0u && tl::violates_sequence(L, 16, 2));
+            // the eighth state: 0 -> 1 makes 15, 1 -> 0 would make 16 -- agent 0's field holds 15, not 16 & 15 = 0 with a carry into agent 1's
+            if (state == 8) CHECK(L == (0xFFu | tl::REACHED));
+        }
+        {  // fixed cases: fields of 8 .. 15, the boundary between N = 15 and N = 16 (what long-trails stores on the device)
+            int b15 = tl::WALK_BUDGET, b16 = tl::WALK_BUDGET;
+            CHECK(tl::layer_update(0xDDu, pair, 16, 2, b16) == 0xFFu && !tl::violates_sequence(0xFFu, 16, 2));  // (13, 13): two more each, stored under N = 16
+            CHECK((tl::layer_update(0xDDu, pair, 15, 2, b15) & tl::REACHED) != 0u && tl::violates_sequence(0xFFu, 15, 2));  // ... and a sequence of 15
+            CHECK(b16 == tl::WALK_BUDGET - 4 && b15 == tl::WALK_BUDGET - 2);  // N = 15 stops at its second extension, 1 -> 0 at length 15
+            for (int N = 9; N <= 16; N++) {  // one arc from a trail of N - 2: N - 1 is stored, whatever the field; one more arc is a sequence
+                int budget = tl::WALK_BUDGET;
+                const uint32_t before = (uint32_t)(N - 2) << 12;
+                const uint32_t after = tl::layer_update(before, (uint64_t)1 << (8 * 3 + 5), N, 6, budget);
+                CHECK(after == (before | (uint32_t)(N - 1) << 20) && !tl::violates_sequence(after, N, 6) && tl::violates_sequence(after, N - 1, 6));
+                const uint32_t over = tl::layer_update(after, (uint64_t)1 << (8 * 5 + 4), N, 6, budget);
+                CHECK((over & tl::REACHED) != 0u && tl::field(over, 4) == (uint32_t)(N < 15 ? N : 15) && (over & 0x7F000000u) == 0u);
+            }
+            // a trail of 16 into agent 5's field, bits 20-23: clamped to 15, nothing carried into bit 24
+            int budget = tl::WALK_BUDGET;
+            CHECK(tl::layer_update(0xFu << 12, (uint64_t)1 << (8 * 3 + 5), 16, 6, budget) == (0xFu << 12 | 0xFu << 20 | tl::REACHED));
         }
         int budget = tl::WALK_BUDGET;
         L = tl::layer_update(0u, (uint64_t)1 << (8 * 3 + 5), 2, 6, budget);  // one edge: length 1, in agent 5's field

@@ -5,7 +5,11 @@ no test here walks a search in Python: per map length, per-depth counters and st
 its mode; the goal's help edges or trail equal to the replay's.
 
 Set X (six agents: 15 625 joint actions per state, frontiers of several hundred records) takes tens of thousands of pieces at
-envs_per_map = 256 and 64 -- a few seconds -- and runs at 4096 as well, where a piece holds candidates of several records."""
+envs_per_map = 256 and 64 -- a few seconds -- and runs at 4096 as well, where a piece holds candidates of several records.
+
+Sets L and C (long trails, one layout under four edge rules) carry per-map `changes`: `assert_equals_golden` applies them to the worlds
+the forest is constructed over and to the oracle worlds the plans are replayed on.  What else is asked of them is in
+tests/test_gpu_helpforest_edges.py."""
 import numpy as np
 import pytest
 
@@ -44,12 +48,16 @@ def expected_pieces(refs, n_joint, E):
     return sum(max(-(-r["frontier"][d] * n_joint // E) for r in refs if d < len(r["expanded"])) for d in range(depths))
 
 
-def assert_equals_golden(hf, maps, refs, t_max, mode, param=2, collect_gems=False, **options):
-    res = run(hf, maps, t_max, mode, param, collect_gems, **options)
+def assert_equals_golden(hf, maps, refs, t_max, mode, param=2, collect_gems=False, changes=None, **options):
+    """`maps`: map texts; `changes`: per map the changes of tests/helpgraph_ref.py applied to its world before the forest is constructed
+    (and to the oracle world every plan is replayed on), None: no map is changed."""
+    changes = [None] * len(maps) if changes is None else list(changes)
+    assert len(changes) == len(maps) == len(refs)
+    res = run(hf, [helpforest_ref.world_of(text, c) for text, c in zip(maps, changes)], t_max, mode, param, collect_gems, **options)
     print(f"{mode}-{param} collect_gems={collect_gems} {options}: lengths {res.length.tolist()}, records {res.n_states.tolist()}, pieces {res.pieces}, "
           f"occupancy {res.valid_items}/{res.launched_lanes}")
     for m, (text, ref) in enumerate(zip(maps, refs)):
-        helpforest_ref.assert_map_equals_golden(text, ref, res, m, mode, param, collect_gems)
+        helpforest_ref.assert_map_equals_golden(text, ref, res, m, mode, param, collect_gems, changes=changes[m])
     E, n_joint = options.get("envs_per_map", 256), 5 ** helpgraph_ref.n_agents_of(maps[0])
     assert res.launched_lanes == res.pieces * len(maps) * E
     assert res.valid_items == n_joint * sum(sum(r["frontier"][:len(r["expanded"])]) for r in refs) <= res.launched_lanes
@@ -71,7 +79,7 @@ def test_sets_equal_the_golden_file(hf, name, mode, param, E):
     """Every map's counters and length are the restatement's whatever E is, every plan replays under its mode, the goal's extra words
     are the replay's, status 0.  E = 256: a workgroup per map; 64: four maps per workgroup."""
     s = SETS[name]
-    res = assert_equals_golden(hf, s.maps, golden(s, mode, param), s.t_max, mode, param, s.collect_gems, envs_per_map=E)
+    res = assert_equals_golden(hf, s.maps, golden(s, mode, param), s.t_max, mode, param, s.collect_gems, changes=s.changes, envs_per_map=E)
     assert not res.status.any()
 
 

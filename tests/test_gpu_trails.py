@@ -21,6 +21,9 @@ The shapes at which the kernels can go wrong, by the map that holds them (tests/
   N = 2 everywhere; N = 4 | 5 on two-agent-mutual-compact and N = 7 | 8 on three-beam-cell: the largest N the horizon can reach, and
                             the first that rejects nothing (equal to N = 16)
   gem-detour                collect_gems=True
+  long-trails and every entry with `changes`
+                            trail fields up to 15, a frontier that runs empty, worlds changed before the construction: what they are
+                            for and what else is asked of them is in tests/test_gpu_trails_edges.py; their counters and plans run here too
 
 Catalogue layouts LEFT OUT of the comparison on the device, by name:
   level-6                                 at t_max 21 the default pool of 4 194 304 records overflows, as the plain search's does at depth 11
@@ -49,11 +52,12 @@ ON_THE_DEVICE = ["one-way-detour", "single-laser-asymmetric", "sequence-4-with-m
 
 
 def search_id(s):
-    return f"{s['map']}-t{s['t_max']}-n{s['n']}" + ("-gems" if s["collect_gems"] else "")
+    return f"{s['map']}{trails_ref.changes_label(s.get('changes'))}-t{s['t_max']}-n{s['n']}" + ("-gems" if s["collect_gems"] else "")
 
 
-def recorded(map_name, n, collect_gems=False):
-    return next(s for s in SEARCHES if (s["map"], s["n"], s["collect_gems"]) == (map_name, n, collect_gems))
+def recorded(map_name, n, collect_gems=False, changes=None):
+    """The first recorded search of the map under `changes` (None: the unchanged world) with this N."""
+    return next(s for s in SEARCHES if (s["map"], s["n"], s["collect_gems"], s.get("changes")) == (map_name, n, collect_gems, changes))
 
 
 @pytest.fixture(scope="module")
@@ -68,9 +72,17 @@ def values(plan):
     return None if plan is None else [[a.value for a in row] for row in plan]
 
 
-def run(tr, text, t_max, n, collect_gems=False, **options):
-    """(plan as rows of action values or None, last_stats) of one fresh TrailSolver."""
-    s = tr.TrailSolver(text, t_max, **options)
+def world_of(text, changes=None):
+    """What the solver is constructed over: the map text, or an lle_amd.World with `changes` applied before the construction."""
+    if changes is None:
+        return text
+    from lle_amd import World
+    return trails_ref.apply_changes(World(text), changes)
+
+
+def run(tr, text, t_max, n, collect_gems=False, changes=None, **options):
+    """(plan as rows of action values or None, last_stats) of one fresh TrailSolver over the world under `changes`."""
+    s = tr.TrailSolver(world_of(text, changes), t_max, **options)
     try:
         plan = values(s.find_shortest(f"no-sequence-{n}", collect_gems=collect_gems))
         return plan, s.last_stats
@@ -79,10 +91,10 @@ def run(tr, text, t_max, n, collect_gems=False, **options):
 
 
 def assert_recorded(tr, s, text=None, **options):
-    """One search of the golden file: length, counters and state count equal the restatement's; the plan replays on the oracle with a
-    longest trail below N, and the goal's trail word is the L of that replay."""
+    """One search of the golden file: length, counters and state count equal the restatement's; the plan replays on the oracle (under
+    the entry's `changes`) with a longest trail below N, and the goal's trail word is the L of that replay."""
     text = MAPS[s["map"]] if text is None else text
-    plan, stats = run(tr, text, s["t_max"], s["n"], s["collect_gems"], **options)
+    plan, stats = run(tr, text, s["t_max"], s["n"], s["collect_gems"], s.get("changes"), **options)
     print(f"{search_id(s)} {options}: length {stats['length']} (ref {s['length']}), states {stats['n_states']} (ref {s['states']}), frontier {stats['frontier']}, "
           f"expanded {stats['expanded']}, trails {stats['trail_lengths']}")
     assert stats["length"] == s["length"] and (plan is None) == (s["length"] is None)
@@ -90,7 +102,7 @@ def assert_recorded(tr, s, text=None, **options):
     if plan is None:
         assert stats["trail_lengths"] is None and stats["longest_trail"] is None
     else:
-        L = trails_ref.check_plan(text, plan, s["n"], s["collect_gems"], length=s["length"])
+        L = trails_ref.check_plan(text, plan, s["n"], s["collect_gems"], length=s["length"], changes=s.get("changes"))
         assert tuple(stats["trail_lengths"]) == L and stats["longest_trail"] == max(L) < s["n"], "the goal's trail word is the L of the plan's replay"
     return plan, stats
 

@@ -16,7 +16,7 @@ import lle_amd
 from lle_amd import Map, World, forest, generator, helpforest, helpgraph, solver, trails
 from lle_amd.generator import Asymmetric, Constraint, Convergent, Cooperative, Divergent, Interdependent, Sequential, Solvable
 from tests import helpforest_ref
-from tests.helpforest_ref import SET_G, SET_P, SET_R, SET_S, SETS
+from tests.helpforest_ref import SET_C, SET_G, SET_L, SET_P, SET_R, SET_S, SET_X, SETS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LINE = "S0 . . X"
@@ -330,14 +330,54 @@ def test_satisfied_by_many_paths(monkeypatch):
 # ---------------------------------------------------------------------------------------------------------------- the fixed input sets
 def test_sets_have_the_stated_shapes():
     shapes = {"S": (4, 6, 3, 1, 0, 8, 6), "P": (5, 9, 2, 2, 0, 8, 8), "R": (6, 6, 3, 2, 0, 5, 5), "Q": (6, 6, 3, 3, 0, 2, 10), "X": (4, 8, 6, 2, 0, 2, 3),
-              "G": (4, 5, 2, 2, 1, 2, 8)}
+              "G": (4, 5, 2, 2, 1, 2, 8), "L": (4, 6, 2, 2, 0, 3, 24), "C": (4, 4, 2, 2, 0, 4, 8)}
+    assert set(shapes) == set(SETS)
     for name, (h, w, agents, sources, gems, count, t_max) in shapes.items():
         s = SETS[name]
-        assert len(s.maps) == count == len(s.names) and s.t_max == t_max
+        assert len(s.maps) == count == len(s.names) == len(s.changes) and s.t_max == t_max
         assert {forest.shape_key(Map(t)) for t in s.maps} == {forest.shape_key(Map(s.maps[0]))}, name
         m = Map(s.maps[0])
         assert (m.height, m.width, m.n_agents, m.n_sources, m.n_gems) == (h, w, agents, sources, gems), name
     assert SET_G.collect_gems and not SET_S.collect_gems
+    assert all(s.changes == (None,) * len(s.maps) for name, s in SETS.items() if name not in "LC")
+    assert SET_L.modes == (("no-sequence", 8), ("no-sequence", 15), ("no-sequence", 16), ("standard", 2)) and SET_X.modes[-2:] == (("no-sequence", 2), ("no-sequence", 3))
+    assert SET_C.modes == (("standard", 2), ("no-mutual", 2), ("no-sequence", 2), ("no-sequence", 3))
+
+
+def test_sets_l_and_c_differ_where_the_device_could_confuse_their_maps():
+    """Set C is ONE layout four times: the texts are equal, the worlds are not, and every map has its own (length, records) under
+    no-sequence-2 -- a forest that reads another map's edge rule gives another map's answer.  Set L's first two maps are one layout too,
+    and its third is another one: a wrong cell-table offset reads other tiles."""
+    assert len(set(SET_C.maps)) == 1 and SET_C.changes == (None, helpforest_ref.OFF1, helpforest_ref.OFF0, helpforest_ref.RECOLOUR1)
+    assert SET_C.names == ("two-agent-mutual-compact", "two-agent-mutual-compact-source1-off", "two-agent-mutual-compact-source0-off",
+                           "two-agent-mutual-compact-source1-colour0")
+    rows = GOLDEN["C"]["no-sequence/2"]
+    assert [(r["length"], r["states"]) for r in rows] == [(None, 100), (5, 164), (5, 130), (None, 107)] and GOLDEN["C"]["no-mutual/2"] == rows
+    assert [(r["length"], r["states"]) for r in GOLDEN["C"]["no-sequence/3"]] == [(5, 119), (5, 164), (5, 130), (None, 107)]
+    for key in GOLDEN["C"]:
+        assert len({(r["length"], r["states"]) for r in GOLDEN["C"][key]}) == 4, key
+    # the worlds the device is given: the sources as the changes leave them
+    worlds = SET_C.worlds
+    assert worlds[0] == SET_C.maps[0] and all(isinstance(w, World) for w in worlds[1:])
+    assert [[(s.is_enabled, s.agent_id) for s in sorted(w.laser_sources, key=lambda s: s.laser_id)] for w in worlds[1:]] == \
+        [[(True, 0), (False, 1)], [(False, 0), (True, 1)], [(True, 0), (True, 0)]]
+    assert SET_L.maps[0] == SET_L.maps[1] != SET_L.maps[2] and SET_L.changes == (None, helpforest_ref.OFF1, None)
+    for n in (8, 15, 16):
+        first, second, third = GOLDEN["L"][f"no-sequence/{n}"]
+        assert (first["length"], first["states"], len(first["expanded"]), first["frontier"][-1]) == (None, 100 + 76 * (n - 2), n + 5, 0)
+        assert (second["length"], second["states"], len(second["expanded"])) == (None, 198, 8)
+        assert (third["length"], third["states"], len(third["expanded"])) == (5, 126, 5)  # solved at depth 5 while the first map walks N + 5 levels
+    assert [(r["length"], r["states"]) for r in GOLDEN["L"]["standard/2"]] == [(None, 203), (None, 198), (5, 123)]
+    # the embedding gives the small layout's counters: set L's third map is set C's first at every depth both walk, set P's first too
+    for key in ("standard/2",):
+        assert GOLDEN["L"][key][2] == GOLDEN["C"][key][0] == GOLDEN["P"][key][0]
+    assert GOLDEN["C"]["no-sequence/3"][0] == GOLDEN["P"]["no-sequence/3"][0] and GOLDEN["C"]["no-sequence/2"][0] == GOLDEN["P"]["no-sequence/2"][0]
+    # six agents under no-sequence-3: the single solver's recorded searches, in a frame of walls
+    from tests import trails_ref
+    single = {(c["map"], c["n"]): c for c in trails_ref.load_cases()["searches"] if "changes" not in c}
+    for m, name in enumerate(SET_X.names):
+        row, want = GOLDEN["X"]["no-sequence/3"][m], single[(name, 3)]
+        assert (row["length"], row["states"], row["frontier"], row["expanded"]) == (want["length"], want["states"], want["frontier"], want["expanded"])
 
 
 def test_golden_file_holds_what_the_issue_states():
@@ -358,14 +398,36 @@ def test_golden_file_holds_what_the_issue_states():
     assert any(r["states"] > 256 for r in asym) and any(r["states"] <= 256 for r in asym)  # capacity isolation has both kinds of map
 
 
-@pytest.mark.parametrize("name, m", [("S", 0), ("S", 1), ("P", 0), ("R", 3), ("R", 2), ("G", 0), ("G", 1)])
+@pytest.mark.parametrize("name, m", [("S", 0), ("S", 1), ("P", 0), ("R", 3), ("R", 2), ("G", 0), ("G", 1), ("L", 0), ("L", 1), ("L", 2), ("C", 0), ("C", 1), ("C", 2),
+                                     ("C", 3)])
 def test_the_restatements_still_give_the_golden_file(name, m):
-    """A subset (the whole file takes minutes): every mode of seven maps, the catalogue maps of S and P among them."""
+    """A subset (the whole file takes minutes): every mode of seven maps, the catalogue maps of S and P among them, and every map of
+    L and C under its changes."""
     s = SETS[name]
     for mode, param in s.modes:
-        r = helpforest_ref.search(s.maps[m], s.t_max, mode, param, s.collect_gems)
+        r = helpforest_ref.search(s.maps[m], s.t_max, mode, param, s.collect_gems, changes=s.changes[m])
         got = dict(length=r.length, frontier=list(r.frontier), expanded=list(r.expanded), states=r.n_states)
         assert got == GOLDEN[name][helpforest_ref.golden_key(mode, param)][m], (name, m, mode, param)
+
+
+@pytest.mark.parametrize("name, m, size, mode, param", [("L", 2, (20, 20), "standard", 2), ("L", 2, (6, 255), "no-sequence", 16), ("R", 3, (255, 6), "no-sequence", 3),
+                                                        ("R", 3, (20, 20), "no-convergence", 2)], ids=str)
+def test_a_layout_in_either_corner_is_the_same_world(name, m, size, mode, param):
+    """What the far-corner tests of tests/test_gpu_helpforest_edges.py lean on: a set's map in the top-left corner (`embed_top_left`) or in
+    the bottom-right corner (`helpgraph_ref.embed`) of a big map of walls has the counters recorded for the small one."""
+    from tests import helpgraph_ref
+    s, want = SETS[name], GOLDEN[name][helpforest_ref.golden_key(mode, param)][m]
+    for text in (helpforest_ref.embed_top_left(helpforest_ref.MAPS[s.names[m]], *size), helpgraph_ref.embed(s.maps[m], *size)):
+        r = helpforest_ref.search(text, s.t_max, mode, param, changes=s.changes[m])
+        assert dict(length=r.length, frontier=list(r.frontier), expanded=list(r.expanded), states=r.n_states) == want
+
+
+@pytest.mark.parametrize("m", [0, 1])
+def test_the_restatement_gives_set_x_under_no_sequence_3(m):
+    """Six agents, trails of two edges stored: the one mode of set X added after the file was first made (its other modes take a minute)."""
+    r = helpforest_ref.search(SET_X.maps[m], SET_X.t_max, "no-sequence", 3)
+    assert dict(length=r.length, frontier=list(r.frontier), expanded=list(r.expanded), states=r.n_states) == GOLDEN["X"]["no-sequence/3"][m]
+    assert r.trails[5] > 0 and max(r.trails) == 2  # the sixth field, bits 20-23, under an N that stores trails of two edges
 
 
 # ---------------------------------------------------------------------------------------------------------------- helpforest_logic.hpp

@@ -35,11 +35,13 @@ BEYOND_THE_RESTATEMENT = ("level-6", "paper-sequence-2-not-interdependent-3", "t
 
 
 def search_id(s):
-    return f"{s['map']}-t{s['t_max']}-n{s['n']}" + ("-gems" if s["collect_gems"] else "")
+    return f"{s['map']}{trails_ref.changes_label(s.get('changes'))}-t{s['t_max']}-n{s['n']}" + ("-gems" if s["collect_gems"] else "")
 
 
-def recorded(map_name, n, collect_gems=False):
-    return next(s for s in CASES["searches"] if (s["map"], s["n"], s["collect_gems"]) == (map_name, n, collect_gems))
+def recorded(map_name, n, collect_gems=False, changes=None, t_max=None):
+    """The first recorded search of the map under `changes` (None: the unchanged world) with this N (and this t_max)."""
+    return next(s for s in CASES["searches"] if (s["map"], s["n"], s["collect_gems"], s.get("changes")) == (map_name, n, collect_gems, changes)
+                and t_max in (None, s["t_max"]))
 
 
 def test_kat_file_is_what_the_maker_writes():
@@ -62,10 +64,18 @@ def test_kat_file_is_what_the_maker_writes():
                  "paper-convergent-2", "two-agent-mutual-with-detours"):
         assert MAPS[name] == theirs[name]  # the maps both fixtures hold are the same text
     ids = [search_id(s) for s in CASES["searches"]]
-    assert len(set(ids)) == len(ids) == 23
+    assert len(set(ids)) == len(ids) == 23 + 15 + 9
     for s in CASES["searches"]:
         assert s["map"] in MAPS and 2 <= s["n"] <= 16 and sum(s["frontier"]) == s["states"] <= 4540
         assert len(s["expanded"]) == len(s["frontier"]) - 1 and (s["length"] is None or s["length"] == len(s["expanded"]))
+        assert set(s) - {"changes"} == {"map", "t_max", "n", "collect_gems", "length", "states", "frontier", "expanded"}
+    assert [s for s in CASES["searches"] if "changes" not in s][:23] == CASES["searches"][:23], "the entries before long-trails stand where they stood"
+    assert [(s["t_max"], s["n"]) for s in CASES["searches"] if s["map"] == "long-trails" and "changes" not in s] == [(24, n) for n in range(2, 17)]
+    changed = [(s["map"], trails_ref.changes_label(s["changes"]), s["t_max"], s["n"]) for s in CASES["searches"] if "changes" in s]
+    compact = "two-agent-mutual-compact"
+    assert changed == [(compact, "-source1-off", 8, 2), (compact, "-source1-off", 8, 3), (compact, "-source0-off", 8, 2), (compact, "-source0-off", 8, 3),
+                       (compact, "-source1-colour0", 8, 2), (compact, "-source1-colour0", 8, 3), ("long-trails", "-source1-off", 24, 16),
+                       (compact, "-source0-off-source1-off", 8, 2), (compact, "-source0-off-source1-off", 8, 16)]
 
 
 def test_library_exports():
@@ -252,10 +262,11 @@ def test_the_restatement_reproduces_the_reference(text, t_max, n, want):
 
 @pytest.mark.parametrize("s", CASES["searches"], ids=[search_id(s) for s in CASES["searches"]])
 def test_the_restatement_reproduces_the_recorded_searches(s):
-    res = trails_ref.search(MAPS[s["map"]], s["t_max"], s["n"], s["collect_gems"])
+    changes = s.get("changes")
+    res = trails_ref.search(MAPS[s["map"]], s["t_max"], s["n"], s["collect_gems"], changes=changes)
     assert (res.length, res.n_states, res.frontier, res.expanded) == (s["length"], s["states"], s["frontier"], s["expanded"])
     if res.plan is not None:
-        assert trails_ref.check_plan(MAPS[s["map"]], res.plan, s["n"], s["collect_gems"], length=s["length"]) == res.trails
+        assert trails_ref.check_plan(MAPS[s["map"]], res.plan, s["n"], s["collect_gems"], length=s["length"], changes=changes) == res.trails
 
 
 def test_layer_update_from_the_definition():
@@ -306,6 +317,83 @@ def test_the_small_maps_show_what_they_are_named_for():
     assert trails_ref.search(MAPS["six-mutual"], 3, 3).trails == (0, 0, 0, 1, 0, 2) and trails_ref.search(MAPS["six-converge"], 3, 3).trails == (0, 0, 0, 2, 2, 1)
     # gems
     assert recorded("gem-detour", 3, True)["length"] == 7 > recorded("gem-detour", 3)["length"] == 5 and recorded("gem-detour", 2, True)["length"] is None
+
+
+# ------------------------------------------------------------------------------------------------ long trails, changed worlds
+LONG_T_MAX = 24
+
+
+def test_long_trails_store_every_field_up_to_15():
+    """What tests/test_gpu_trails_edges.py leans on, from the restatement itself: for every N in 2 .. 16 long-trails has no plan, stores
+    100 + 76 (N - 2) records whose greatest field is N - 1, and its frontier runs empty at depth N + 5 < t_max -- so every N has its own
+    counters, and a device that clips a field, mis-shifts its stack or compares N off by one gives those of another N or of none."""
+    text = MAPS["long-trails"]
+    results = {n: trails_ref.search(text, LONG_T_MAX, n) for n in range(2, 17)}
+    for n, res in results.items():
+        s = recorded("long-trails", n)
+        assert (s["t_max"], s["length"], s["states"], s["frontier"], s["expanded"]) == (LONG_T_MAX, None, res.n_states, res.frontier, res.expanded)
+        assert res.length is None and res.plan is None and res.trails is None
+        assert res.n_states == 100 + 76 * (n - 2) and res.peak == n - 1
+        assert len(res.expanded) == n + 5 < LONG_T_MAX and len(res.frontier) == n + 6 and res.frontier[-1] == 0 and all(res.frontier[:-1])
+    assert (results[15].n_states, results[16].n_states) == (1088, 1164)
+    assert len({(tuple(r.frontier), tuple(r.expanded)) for r in results.values()}) == 15  # every N has counters of its own
+    last = results[16]
+    assert last.frontier == [1, 3, 6, 13, 35, 68, 74] + [76] * 10 + [75, 70, 48, 11, 0]
+    assert last.expanded == [6, 29, 61, 172, 426, 786, 847] + [865] * 10 + [853, 784, 483, 102]
+    assert max(f * 25 for f in last.frontier) == 1900 and -(-1900 // 64) == 30  # work items of the largest level: 30 pieces of 64
+    assert max(last.expanded) == 865  # of which 865 are joint actions the masks allow
+    # the walls change nothing before the pair is formed: up to depth 4 the levels are two-agent-mutual-compact's
+    assert last.frontier[:5] == recorded("two-agent-mutual-compact", 16)["frontier"][:5]
+    assert trails_ref.is_sequential(text, LONG_T_MAX, 2) is False and trails_ref.is_sequential(text, LONG_T_MAX, 16) is False  # not solvable at all
+
+
+@pytest.mark.parametrize("size, name, n", [((20, 20), "long-trails", 16), ((255, 6), "long-trails", 16), ((6, 255), "long-trails", 3), ((64, 64), "long-trails", 3),
+                                           ((65, 66), "chain-in-one-state", 3), ((6, 255), "chain-in-one-state", 2)], ids=str)
+def test_an_embedded_layout_has_the_small_layouts_counters(size, name, n):
+    """`helpgraph_ref.embed` puts the layout in the far corner of a map of walls: the same world to the restatement, so the GPU tests may
+    hold the device to the small layout's recorded counters on the big map."""
+    from tests import helpgraph_ref
+    s = recorded(name, n)
+    res = trails_ref.search(helpgraph_ref.embed(MAPS[name], *size), s["t_max"], n)
+    assert (res.length, res.n_states, res.frontier, res.expanded) == (s["length"], s["states"], s["frontier"], s["expanded"])
+
+
+def test_one_layout_four_worlds_four_answers():
+    """two-agent-mutual-compact at t_max 8 under no-sequence-2: unchanged, source 1 disabled, source 0 disabled, source 1 recoloured to
+    0 -- four different (length, records), so a search that reads another world's rule gives another world's answer."""
+    from tests import helpgraph_ref
+    text, compact = MAPS["two-agent-mutual-compact"], "two-agent-mutual-compact"
+    maker = importlib.util.spec_from_file_location("make_kat_trails", os.path.join(ROOT, "tests", "golden", "make_kat_trails.py"))
+    mod = importlib.util.module_from_spec(maker)
+    maker.loader.exec_module(mod)
+    variants = [None, mod.OFF1, mod.OFF0, mod.RECOLOUR1]
+    got = []
+    for changes in variants:
+        res = trails_ref.search(text, 8, 2, changes=changes)
+        got.append((res.length, res.n_states))
+        if changes is not None:
+            s = recorded(compact, 2, changes=changes)
+            assert (s["t_max"], s["length"], s["states"]) == (8, res.length, res.n_states)
+    assert got == [(None, 100), (5, 164), (5, 130), (None, 107)] and len(set(got)) == 4
+    # None is the unchanged world, computed once: the entry without `changes` is the same object as before
+    assert trails_ref.search(text, 8, 2, changes=None) is trails_ref.search(text, 8, 2)
+    assert trails_ref.search(text, 6, 2).n_states == recorded(compact, 2, t_max=6)["states"] == 100
+    # the predicate under changes: unchanged every plan holds a mutual pair; without source 1 a plan avoids every trail of two edges
+    assert trails_ref.is_sequential(text, 8, 2) is True and trails_ref.is_sequential(text, 8, 2, changes=mod.OFF1) is False
+    assert trails_ref.is_sequential(text, 8, 2, changes=mod.RECOLOUR1) is False  # (not solvable at all in that world)
+    # every source disabled: no arc anywhere, so every N walks the plain search of the changed world
+    plain = helpgraph_ref.search(text, 8, changes=mod.ALL_OFF)
+    for n in (2, 16):
+        res, s = trails_ref.search(text, 8, n, changes=mod.ALL_OFF), recorded(compact, n, changes=mod.ALL_OFF)
+        assert (res.length, res.frontier, res.expanded, res.peak) == (plain.length, plain.frontier, plain.expanded, 0) == (5, s["frontier"], s["expanded"], 0)
+        assert res.trails == (0, 0) and plain.edges == set() and s["states"] == 151
+    # a plan found in one world is refused in another: the replay is under the entry's changes
+    plan = trails_ref.search(text, 8, 2, changes=mod.OFF1).plan
+    assert trails_ref.check_plan(text, plan, 2, length=5, changes=mod.OFF1) == (0, 1)
+    with pytest.raises(Exception):
+        trails_ref.check_plan(text, plan, 2, changes=None)
+    long_off = trails_ref.search(MAPS["long-trails"], LONG_T_MAX, 16, changes=mod.OFF1)
+    assert (long_off.length, long_off.n_states, long_off.peak) == (None, 198, 1) and long_off.n_states == recorded("long-trails", 16, changes=mod.OFF1)["states"]
 
 
 def test_check_plan_refuses_a_plan_with_a_longer_trail():

@@ -10,7 +10,11 @@ used), written from the definition; nothing here knows bit words, nibbles, curso
 no-sequence-N a trajectory is dropped as soon as max(L) >= N, so every stored L is below N on both sides.
 
 A level is always finished before the search stops on a goal, so `frontier` and `expanded` by depth are reproducible.  Results are
-cached per (map, t_max, N, collect_gems): the CPU and the GPU tests share one computation.
+cached per (map, changes, t_max, N, collect_gems): the CPU and the GPU tests share one computation.
+
+`changes` (optional everywhere; None: the map as its text gives it) has the meaning and the plain-data form of tests/helpgraph_ref.py:
+sources disabled or recoloured and exits moved on the fresh OracleWorld before its reset (`helpgraph_ref.oracle_world`), and on an
+lle_amd.World before a solver is constructed over it (`helpgraph_ref.apply_changes`).
 """
 import itertools
 import json
@@ -18,8 +22,8 @@ import os
 from dataclasses import dataclass, field
 from functools import lru_cache
 
-from oracle import oracle
 from tests import coop_ref, search_ref
+from tests.helpgraph_ref import apply_changes, changes_key, changes_label, oracle_world  # noqa: F401  (re-exported: one meaning of `changes`)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -75,16 +79,16 @@ def layer_update(L, arcs):
 _CACHE = {}
 
 
-def search(text, t_max, n, collect_gems=False):
-    key = (text, int(t_max), int(n), bool(collect_gems))
+def search(text, t_max, n, collect_gems=False, changes=None):
+    key = (text, changes_key(changes), int(t_max), int(n), bool(collect_gems))
     if key not in _CACHE:
-        _CACHE[key] = _search(text, int(t_max), int(n), bool(collect_gems))
+        _CACHE[key] = _search(text, int(t_max), int(n), bool(collect_gems), changes)
     return _CACHE[key]
 
 
-def _search(text, t_max, n, collect_gems):
+def _search(text, t_max, n, collect_gems, changes=None):
     assert n >= 2
-    world = oracle.OracleWorld(text)
+    world = oracle_world(text, changes)
     A = world.n_agents
     world.reset()
     res = Result(None, None, [1], [])
@@ -135,10 +139,10 @@ def _search(text, t_max, n, collect_gems):
     return res
 
 
-def replay_trails(text, plan):
+def replay_trails(text, plan, changes=None):
     """(L after the last state of `plan` by `layer_update`, the temporal edges (helper, beneficiary, t), the world) on a fresh oracle
-    world; asserts that nobody dies."""
-    world = oracle.OracleWorld(text)
+    world with `changes` applied; asserts that nobody dies."""
+    world = oracle_world(text, changes)
     world.reset()
     assert all(world.alive())
     arcs = coop_ref.detect(world)
@@ -154,14 +158,14 @@ def replay_trails(text, plan):
     return L, edges, world
 
 
-def check_plan(text, plan, n, collect_gems=False, length=None):
-    """Replay `plan` (rows of action values) on a fresh oracle world: nobody dies, everybody arrives, and the longest trail of the
+def check_plan(text, plan, n, collect_gems=False, length=None, changes=None):
+    """Replay `plan` (rows of action values) on a fresh oracle world (under `changes`): nobody dies, everybody arrives, and the longest trail of the
     replay's temporal edges -- by the package's host-side graph, lle_amd.characterization.TemporalCooperationGraph, which shares no
     code with `layer_update` -- is shorter than `n`.  Returns L of the last state (whose maximum is that longest trail)."""
     from lle_amd.characterization import DependencyEdge, TemporalCooperationGraph
     if length is not None:
         assert len(plan) == length, (len(plan), length)
-    L, edges, world = replay_trails(text, plan)
+    L, edges, world = replay_trails(text, plan, changes)
     assert all(world.arrived()), "not every agent has arrived"
     if collect_gems:
         assert all(world.gems_collected())
@@ -172,11 +176,11 @@ def check_plan(text, plan, n, collect_gems=False, length=None):
 
 
 # ---------------------------------------------------------------------------------------------- the reference's predicate
-def is_sequential(text, t_max, length):
+def is_sequential(text, t_max, length, changes=None):
     """The reference's WorldCharacterizer.is_sequential (world_characterization.py) answered with this search: solvable within t_max
     and no plan within t_max avoids every trail of `length` edges.  (The reference asks the shortest plan's profile first: a plan that
     holds such a trail is implied by "no plan avoids it", so the answers are the same.)"""
     from tests import helpgraph_ref
-    if helpgraph_ref.search(text, t_max).length is None:
+    if helpgraph_ref.search(text, t_max, changes=changes).length is None:
         return False
-    return search(text, t_max, length).length is None
+    return search(text, t_max, length, changes=changes).length is None
