@@ -73,7 +73,8 @@ enum {
 
 /* ---- per-environment result codes (buffer LLE_BUF_ERR), the batched form of `RuntimeWorldError`
  * (src/core/errors.rs:6-45).  An env with a non-zero code after `step` is left untouched and emits no
- * event, like the reference (src/core/world.rs:436-453). */
+ * event, like the reference (src/core/world.rs:436-453): its state keeps its bytes; its row of LLE_BUF_OBS and its
+ * evcount / events / done / reward entries are written like those of every other env (no event, zero counts). */
 enum {
     LLE_ENV_OK = 0,
     /* 1..LLE_MAX_AGENTS: InvalidAction by agent (code - 1), lowest offending agent id */
@@ -256,7 +257,9 @@ int64_t lle_batch_snapshot_bytes(const lle_batch* b);
 int lle_batch_snapshot(lle_batch* b, void* dst_dev, void* stream);
 int lle_batch_restore(lle_batch* b, const void* src_dev, void* stream);
 
-/* World.reset (src/core/world.rs:411-432) for every env, or for envs whose byte in env_mask (device, u8[n]) != 0. */
+/* World.reset (src/core/world.rs:411-432) for every env, or for envs whose byte in env_mask (device, u8[n]) != 0.
+ * An env outside the mask keeps every byte of its state and of its err / evcount / events / done; its row of LLE_BUF_OBS is
+ * rewritten all the same, from its own current state (the launch rebuilds the rows of all its envs). */
 int lle_batch_reset(lle_batch* b, const uint8_t* env_mask_dev, void* stream);
 
 /* World.step (src/core/world.rs:435-475) + Layered.observe (python/lle/observations.py:254-266) for every env. */
@@ -351,7 +354,7 @@ int lle_batch_set_sources(lle_batch* b, const uint8_t* colours_dev, const uint32
 int lle_batch_reset_sources(lle_batch* b, const uint8_t* colours_dev, const uint32_t* enabled_dev, const uint8_t* env_mask_dev,
                             uint32_t flags, void* stream);
 
-/* Rebuild LLE_BUF_OBS from the current state. */
+/* Rebuild LLE_BUF_OBS from the current state, and LLE_BUF_DONE with it (a function of the state). */
 int lle_batch_observe(lle_batch* b, void* stream);
 
 /* ---- batches of SEVERAL maps (e.g. one generated map per block of environments; SURVEY.md section 8(d), config 5 variant)

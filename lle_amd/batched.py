@@ -111,7 +111,7 @@ class BatchedWorld:
         if nbytes <= 0:
             raise RuntimeError(L.lle_last_error().decode())
         def create():
-            arena = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+            arena = self._alloc_arena(nbytes)
             base = arena[(-arena.data_ptr()) % 256:][:nbytes]
             h = L.lle_batch_create_opt(handles, len(self.maps), self.envs_per_map, self.device.index or 0, base.data_ptr(), nbytes, C.byref(opt),
                                        self._stream())
@@ -137,6 +137,11 @@ class BatchedWorld:
             autotune_ms = float(env_ms) if env_ms not in (None, "") else (self.AUTOTUNE_MS if self.n_envs >= self.AUTOTUNE_MIN_ENVS else 0.0)
         if autotune_ms and autotune_ms > 0 and envs_per_wave is None:  # (envs_per_wave selects the diagnostic lane-per-env kernel: nothing to tune)
             self.autotune(autotune_ms)
+
+    def _alloc_arena(self, nbytes):
+        """Device memory for an arena of `nbytes` bytes: a uint8 tensor with room for the 256-byte alignment lle_batch_create asks for (the
+        batch takes the first 256-byte boundary in it).  A method so that a harness can hand the batch memory it watches (tests/arena_footprint.py)."""
+        return torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
 
     def _place(self, create, k):
         """k candidate arenas side by side (all alive until every one is timed: distinct physical memory), the row-fill

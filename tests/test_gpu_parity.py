@@ -653,18 +653,24 @@ def test_autotune_many_agents_keeps_the_counter_slots(oracle_mod):
     LLE_BUF_STATS (one slot per wavefront of AT LEAST four environments) is too short: the trial launches wrote their counters over
     REQ_POS / REQ_GEMS / REQ_ALIVE / REWARD / SRC_COLOUR.  Now no launch runs below four environments per wavefront.  A 14-agent map
     (step_kernel<16, .>, cap 4) and config 5 (8 agents, cap 8) at 65 536 / 32 768 environments: the buffers behind LLE_BUF_STATS keep
-    a sentinel pattern through the sweep, LLE_STEP_EPW=1 / 2 are ignored, and the counters of a rollout add up to the events."""
+    a sentinel pattern through the sweep (and, tests/arena_footprint.py: no byte of the whole guarded arena changes outside what the trial
+    steps and the closing reset may write), LLE_STEP_EPW=1 / 2 are ignored, and the counters of a rollout add up to the events."""
     import torch
 
     from lle_amd import BatchedWorld, _capi, mapgen
+    from tests import arena_footprint
 
     for text, n in ((EXTRA_MAPS["many_agents"], 65536), (mapgen.config5(1), 32768)):
-        bw = BatchedWorld(text, n, autotune_ms=0)
+        bw, fp = arena_footprint.guarded_world(text, n, autotune_ms=0)
         assert bw.kernel_info()["envs_per_wave"] >= 4
         guard = [bw.req_pos, bw.req_gems, bw.req_alive, bw.src_colour, bw.src_enabled]
         for g in guard:
             g.fill_(PATTERN[g.element_size()])
-        tuned = bw.autotune(budget_ms=8.0)
+        # the whole arena around the sweep (tests/arena_footprint.py): the guards on both sides of it hold, and every byte that changes lies
+        # in a buffer a sampled step with auto-reset, the zeroed counters or the closing reset may write -- none in req_*, src_*, internal
+        with fp.watch(arena_footprint.RULES["autotune"], bulk=True):
+            tuned = bw.autotune(budget_ms=8.0)
+        assert not any(k[0].startswith(("req_", "src_", "internal")) for k in fp.found), fp.found
         assert tuned["envs_per_wave"] >= 4, tuned
         if "envs_per_wave:" in tuned["log"]:  # (16 lanes per environment: four environments per wavefront is the only choice, nothing is swept)
             swept = tuned["log"].split("envs_per_wave:")[1].split("->")[0]
