@@ -7,8 +7,9 @@
 // lle_batch_create_multi, in which map m owns the environments [m * E, (m + 1) * E); per map a segment of the pool (n_words + 2 arrays
 // of `cap` words, whichever kind runs), parent, action, a table segment, eight counters -- and the map's OWN static data: its cell
 // table (H * W words) and its edge rule.  Lanes, segments and the fates of a map are ../forest/forest_logic.hpp's, the edge rule and
-// the modes ../helpgraph/helpgraph_logic.hpp's, the walk ../trails/trails_logic.hpp's; helpforest_logic.hpp holds what a LOCAL tag
-// (TAG_BIT | index inside the map's block) means for the occupant comparison, and the fate of a map whose walk ran out of budget.
+// the modes ../helpgraph/helpgraph_logic.hpp's, the walk ../trails/trails_logic.hpp's.  Both kinds (hl::HelpKind, tl::TrailKind) run
+// through the same code of ../search/search_logic.hpp: a LOCAL tag (TAG_BIT | index inside the map's block) is taken apart by sl::Piece,
+// sl::occupant_is compares; helpforest_logic.hpp holds the fate of a map whose walk ran out of budget.
 //
 // A piece is four launches over all n_maps * E lanes:
 //   hf_expand        lane k serves map k / E and item piece * E + k % E of it, or idles (valid = 0, nothing else written)
@@ -29,22 +30,26 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/lle_helpforest.h"
-#include "../search/search_device.hpp"
+#include "../search/search_core.hpp"
 #include "helpforest_logic.hpp"
 
 namespace lle {
 
 namespace sl = lle_search_logic;
 namespace sd = lle_search_device;
+namespace sc = lle_search_core;
 namespace fl = lle_forest_logic;
 namespace hl = lle_helpgraph_logic;
 namespace tl = lle_trails_logic;
 namespace hfl = lle_helpforest_logic;
 
 constexpr int HF_THREADS = 256;
+template <int KIND>
+using KindOf = std::conditional_t<KIND == hfl::KIND_HELP, hl::HelpKind, tl::TrailKind>;
 
 struct HfParams {
     sl::BatchView b;       // the batch (include/lle_hip.h buffer descriptors, read once)
@@ -75,14 +80,20 @@ struct HfParams {
     uint64_t piece;
 };
 
-struct MapCells {  // one map's cell table, in global memory
-    const uint32_t* cells;
-    __host__ __device__ uint32_t operator()(int c) const { return cells[c]; }
-};
-
 __device__ inline uint32_t* pool_segment(const HfParams& p, int64_t map) { return p.pool + hfl::pool_segment_offset(map, p.lay.n_words, p.cap); }
-__device__ inline MapCells map_cells(const HfParams& p, int64_t map) { return MapCells{p.cells + (uint64_t)map * (uint64_t)p.H * (uint64_t)p.W}; }
+__device__ inline sc::Cells map_cells(const HfParams& p, int64_t map) { return sc::Cells{p.cells + (uint64_t)map * (uint64_t)p.H * (uint64_t)p.W}; }
 __device__ inline int64_t lane_index() { return (int64_t)blockIdx.x * HF_THREADS + threadIdx.x; }
+// The kind a map searches with in this run: its own edge rule, the run's mode and param (k of a help mode, or N).
+template <int KIND>
+__device__ inline KindOf<KIND> map_kind(const HfParams& p, int64_t map) {
+    if constexpr (KIND == hfl::KIND_HELP) return hl::HelpKind{p.rules[map], p.mode, p.param};
+    else return tl::TrailKind{p.rules[map], p.param};
+}
+// A value as a lane keeps it between insert and commit, and as the host hands a reset state's over: a 64-bit word, the low one first.
+template <class Kind>
+__device__ inline typename Kind::Value value_of(uint32_t lo, uint32_t hi) {
+    return (typename Kind::Value)((uint64_t)lo | (uint64_t)hi << 32);
+}
 
 // One lane per map: the record of the map's first environment (freshly reset) into roots.
 __global__ __launch_bounds__(HF_THREADS) void hf_roots(HfParams p) {
@@ -102,16 +113,9 @@ __global__ __launch_bounds__(HF_THREADS) void hf_seed(HfParams p) {
     const uint32_t* root = p.roots + m * r.n_words;
     uint32_t* seg = pool_segment(p, m);
     for (int w = 0; w < r.n_words; w++) seg[(uint64_t)w * p.cap] = root[w];
-    const uint32_t x0 = p.root_extra[2 * m], x1 = p.root_extra[2 * m + 1];
-    auto rec = [&](int w) { return root[w]; };
-    uint64_t h;
-    if constexpr (KIND == hfl::KIND_HELP) {
-        hl::store_pool_help(seg, p.cap, r, 0, hl::help_of(x0, x1));
-        h = sl::hash_record(hl::key_with_help(rec, r.n_key, hl::help_of(x0, x1)), r.n_key + 2);
-    } else {
-        tl::store_pool_trail(seg, p.cap, r, 0, x0);
-        h = sl::hash_record(tl::key_with_trail(rec, r.n_key, x0), r.n_key + 1);
-    }
+    const auto x = KindOf<KIND>::words(value_of<KindOf<KIND>>(p.root_extra[2 * m], p.root_extra[2 * m + 1]));
+    sl::store_pool_extra(seg, p.cap, r, 0, x);
+    const uint64_t h = sl::hash_record(sl::key_with_extra([&](int w) { return root[w]; }, r.n_key, x), r.n_key + KindOf<KIND>::EXTRA);
     p.table[fl::table_base(m, p.slots) + ((uint32_t)h & (uint32_t)(p.slots - 1))] = 0u;
     p.parent[fl::state_index(m, p.cap, 0)] = 0xFFFFFFFFu;
     p.action[fl::state_index(m, p.cap, 0)] = 0;
@@ -151,35 +155,20 @@ __global__ __launch_bounds__(HF_THREADS) void hf_insert(HfParams p) {
     if (sl::anybody_dead(rec(r.w_bits), r.A)) return;
     const fl::MapDescriptor d = p.desc[map];
     const uint32_t* seg = pool_segment(p, map);
-    const hfl::MapPiece who{p.b, fl::env_index(map, p.E, 0), (uint32_t)p.E, seg, p.cap, p.cap, d.first_state, p.piece * (uint64_t)p.E, d.items, p.n_joint, p.param};
-    const uint64_t parent = hfl::tag_parent(who, local);  // < the frontier's end <= cap: the lane is not idle
-    const MapCells cell = map_cells(p, map);
-    const hl::EdgeRule rule = p.rules[map];
-    uint32_t* table = p.table + fl::table_base(map, p.slots);
-    const uint32_t mask = (uint32_t)(p.slots - 1);
-    int64_t slot;
-    uint64_t extra;
-    if constexpr (KIND == hfl::KIND_HELP) {
-        const uint64_t help = hl::successor_help(p.b, r, rule, cell, seg, p.cap, parent, k);
-        if (hl::violates(help, p.mode, p.param, r.A)) return;
-        const auto me = hl::key_with_help(rec, r.n_key, help);
-        auto same_as = [&](uint32_t occupant) { return hfl::help_occupant_is(who, r, rule, cell, occupant, me); };
-        slot = sl::table_insert(table, mask, sl::hash_record(me, r.n_key + 2), sl::TAG_BIT | local, sd::SlotLoad{}, sd::SlotCas{}, same_as);
-        extra = help;
-    } else {
-        const uint64_t edges = hl::state_edges(rec, r, rule, cell);
-        int budget = tl::WALK_BUDGET;
-        const uint32_t trail = tl::successor_trail(seg, p.cap, r, parent, edges, p.param, budget);
-        if (budget < 0) {  // the walk did not finish: this map has no answer
-            atomicAdd(&counters[hfl::CNT_DENSE], 1ull);
-            return;
-        }
-        if (tl::violates_sequence(trail, p.param, r.A)) return;
-        const auto me = tl::key_with_trail(rec, r.n_key, trail);
-        auto same_as = [&](uint32_t occupant) { return hfl::trail_occupant_is(who, r, occupant, me, edges); };
-        slot = sl::table_insert(table, mask, sl::hash_record(me, r.n_key + 1), sl::TAG_BIT | local, sd::SlotLoad{}, sd::SlotCas{}, same_as);
-        extra = trail;
+    const sl::Piece who{p.b, fl::env_index(map, p.E, 0), (uint32_t)p.E, seg, p.cap, p.cap, d.first_state, p.piece * (uint64_t)p.E, d.items, p.n_joint};
+    const uint64_t parent = sl::tag_parent(who, local);  // < the frontier's end <= cap: the lane is not idle
+    const auto kind = map_kind<KIND>(p, map);
+    const uint64_t arcs = kind.state(rec, r, map_cells(p, map));
+    typename KindOf<KIND>::Value extra;
+    if (!kind.successor(seg, p.cap, r, parent, arcs, &extra)) {  // the walk did not finish: this map has no answer
+        atomicAdd(&counters[hfl::CNT_DENSE], 1ull);
+        return;
     }
+    if (kind.violates(extra, r.A)) return;
+    const auto me = sl::key_with_extra(rec, r.n_key, kind.words(extra));
+    auto same_as = [&](uint32_t occupant) { return sl::occupant_is(who, r, kind, arcs, occupant, me); };
+    const int64_t slot = sl::table_insert(p.table + fl::table_base(map, p.slots), (uint32_t)(p.slots - 1), sl::hash_record(me, r.n_key + KindOf<KIND>::EXTRA),
+                                          sl::TAG_BIT | local, sd::SlotLoad{}, sd::SlotCas{}, same_as);
     if (slot >= 0) {
         p.win_slot[k] = (uint32_t)slot;
         p.cand_extra[k] = extra;  // for hf_commit, a later launch; no lane of this launch reads it
@@ -204,17 +193,15 @@ __global__ __launch_bounds__(HF_THREADS) void hf_commit(HfParams p) {
     const sl::RecordLayout& r = p.lay;
     const sl::EnvRecord rec{p.b, r, k};
     uint32_t* seg = pool_segment(p, map);
-    const uint64_t extra = p.cand_extra[k];
+    const auto kind = map_kind<KIND>(p, map);
+    const auto extra = (typename KindOf<KIND>::Value)p.cand_extra[k];
     sl::copy_record(p.b, r, k, seg, p.cap, idx);
-    if constexpr (KIND == hfl::KIND_HELP) hl::store_pool_help(seg, p.cap, r, idx, extra);
-    else tl::store_pool_trail(seg, p.cap, r, idx, (uint32_t)extra);
+    sl::store_pool_extra(seg, p.cap, r, idx, kind.words(extra));
     const uint64_t item = p.piece * (uint64_t)p.E + (uint64_t)(k % p.E);
     p.parent[fl::state_index(map, p.cap, idx)] = p.desc[map].first_state + (uint32_t)(item / p.n_joint);
     p.action[fl::state_index(map, p.cap, idx)] = (uint16_t)(item % p.n_joint);
     p.table[fl::table_base(map, p.slots) + slot] = (uint32_t)idx;
-    bool goal = sl::is_goal(rec(r.w_bits), rec(r.w_gems), r, p.collect_gems != 0u, p.G);
-    if constexpr (KIND == hfl::KIND_HELP) goal = goal && hl::accepts(extra, p.mode, r.A);
-    if (goal) atomicMin(&counters[fl::CNT_GOAL], idx);
+    if (sl::is_goal(rec(r.w_bits), rec(r.w_gems), r, p.collect_gems != 0u, p.G) && kind.accepts(extra, r.A)) atomicMin(&counters[fl::CNT_GOAL], idx);
 }
 
 // One lane per map; desc[m]: active = solved, first_state = the goal record, items = the plan's length (<= plan_rows).
@@ -261,6 +248,7 @@ namespace hl = lle_helpgraph_logic;
 namespace tl = lle_trails_logic;
 namespace hfl = lle_helpforest_logic;
 namespace sd = lle_search_device;
+namespace sc = lle_search_core;
 using sd::DeviceGuard;
 using sd::fail;
 using sd::g_error;
@@ -289,38 +277,6 @@ struct MapRun {  // one map in the last run
     std::vector<uint8_t> plan;
     uint32_t extra[2] = {0u, 0u};  // of the plan's last state
 };
-
-// One map's cell table appended to `cells`, and its edge rule (helpgraph_logic.hpp: EdgeRule), from lle_map_laser_tiles / lle_map_sources.
-bool build_rule(const lle_map* map, const lle_map_info& info, std::vector<uint32_t>& cells, hl::EdgeRule& rule, std::string& err) {
-    const int H = info.height, W = info.width;
-    std::vector<lle_source_info> src((size_t)std::max(0, lle_map_sources(map, nullptr, 0)));
-    lle_map_sources(map, src.data(), (int)src.size());
-    if ((int)src.size() > hl::MAX_SOURCES) {
-        err = "more than 32 sources: a cell's word has one bit per source";
-        return false;
-    }
-    rule.A = info.n_agents;
-    rule.H = H;
-    rule.W = W;
-    rule.enabled = 0u;
-    for (int a = 0; a < sl::MAX_AGENTS; a++) rule.mine[a] = 0u;
-    for (size_t l = 0; l < src.size(); l++) {
-        if (src[l].enabled) rule.enabled |= 1u << l;
-        if (src[l].agent_id >= 0 && src[l].agent_id < sl::MAX_AGENTS) rule.mine[src[l].agent_id] |= 1u << l;
-    }
-    const size_t base = cells.size();
-    cells.resize(base + (size_t)H * W, 0u);
-    std::vector<lle_laser_tile> tiles((size_t)std::max(0, lle_map_laser_tiles(map, nullptr, 0)));
-    lle_map_laser_tiles(map, tiles.data(), (int)tiles.size());
-    for (const auto& t : tiles) {
-        if (t.i < 0 || t.i >= H || t.j < 0 || t.j >= W || t.laser_id < 0 || t.laser_id >= (int)src.size()) {
-            err = "laser tile out of range";
-            return false;
-        }
-        cells[base + (size_t)t.i * W + t.j] |= 1u << t.laser_id;
-    }
-    return true;
-}
 
 }  // namespace
 
@@ -445,7 +401,7 @@ lle_helpforest* lle_helpforest_create(const lle_map* const* maps, int n_maps, co
     std::vector<hl::EdgeRule> rules((size_t)n_maps);
     for (int m = 0; m < n_maps; m++) {
         std::string why;
-        if (!build_rule(maps[m], info, cells, rules[(size_t)m], why)) return refuse(LLE_ERR_UNSUPPORTED, why + " (map " + std::to_string(m) + ")");
+        if (!sc::build_rule(maps[m], info, cells, rules[(size_t)m], why)) return refuse(LLE_ERR_UNSUPPORTED, why + " (map " + std::to_string(m) + ")");
     }
     int device = -1;
     if (sd::choose_device(opt ? opt->device : -1, "no HIP device: the help forest runs on the GPU only (there is no CPU fallback)", &device) != LLE_OK)

@@ -1,6 +1,6 @@
 // helpgraph_logic.hpp -- the parts of the help-graph search (helpgraph.hip, liblle_helpgraph.so) that run the same on the host and on the
-// device: the help edges of one state, what a mode rejects and accepts, and the functors that append the two help words to a record
-// of ../search/search_logic.hpp.  tests/hostsim/helpgraph_logic.cpp drives all of it under sanitizers.
+// device: the help edges of one state, what a mode rejects and accepts, and HelpKind: the two help words as the extra words of a
+// record of ../search/search_logic.hpp.  tests/hostsim/helpgraph_logic.cpp drives all of it under sanitizers.
 //
 // A HELP VALUE is 48 bits: byte h = the beneficiaries of helper h, bit 8 h + b set iff h has helped b in some state of the trajectory.
 // It travels as two 32-bit words (lo, hi) that are part of a record's identity: hashed and compared after the search's key words.
@@ -106,71 +106,38 @@ LLE_SEARCH_HD bool accepts(uint64_t help, int mode, int A) {
     return true;
 }
 
-// ---- records with help words
-// The IDENTITY of a record: the n_key key words of `rec`, then the two help words.  What hash_record and same_record read, with
-// n_key + 2 words.
+// ---- records with help words: the help kind of ../search/search_logic.hpp, two extra words (lo, hi)
+LLE_SEARCH_HD sl::ExtraWords<2> help_words(uint64_t help) { return sl::ExtraWords<2>{{help_lo(help), help_hi(help)}}; }
+// The IDENTITY of a record: the n_key key words of `rec`, then the two help words.
 template <class Record>
-struct KeyWithHelp {
-    const Record& rec;
-    int n_key;
-    uint32_t lo, hi;
-    LLE_SEARCH_HD uint32_t operator()(int w) const { return w < n_key ? rec(w) : w == n_key ? lo : hi; }
-};
-template <class Record>
-LLE_SEARCH_HD KeyWithHelp<Record> key_with_help(const Record& rec, int n_key, uint64_t help) {
-    return KeyWithHelp<Record>{rec, n_key, help_lo(help), help_hi(help)};
+LLE_SEARCH_HD sl::KeyWithExtra<Record, 2> key_with_help(const Record& rec, int n_key, uint64_t help) {
+    return sl::key_with_extra(rec, n_key, help_words(help));
 }
-// Record s of a pool of `stride` records: the n_words words of search_logic.hpp's record, then the help words at n_words and
-// n_words + 1.  They live only here: the batch has no buffer for them.
+// The help words of record s of a pool of `stride` records, at n_words and n_words + 1 behind search_logic.hpp's record.
 LLE_SEARCH_HD uint64_t pool_help(const uint32_t* pool, uint64_t stride, const sl::RecordLayout& r, uint64_t s) {
-    return help_of(pool[(uint64_t)r.n_words * stride + s], pool[(uint64_t)(r.n_words + 1) * stride + s]);
+    const sl::ExtraWords<2> x = sl::pool_extra<2>(pool, stride, r, s);
+    return help_of(x.w[0], x.w[1]);
 }
 LLE_SEARCH_HD void store_pool_help(uint32_t* pool, uint64_t stride, const sl::RecordLayout& r, uint64_t s, uint64_t help) {
-    pool[(uint64_t)r.n_words * stride + s] = help_lo(help);
-    pool[(uint64_t)(r.n_words + 1) * stride + s] = help_hi(help);
-}
-struct PoolKeyWithHelp {  // the identity of pool record s
-    const uint32_t* pool;
-    uint64_t stride, s;
-    int n_key, n_words;
-    LLE_SEARCH_HD uint32_t operator()(int w) const { return pool[(uint64_t)(w < n_key ? w : n_words + (w - n_key)) * stride + s]; }
-};
-
-// The help value of the successor in environment k of a piece: its parent's, from the pool, or-ed with the edges of the state in the
-// batch.  Both were written by earlier launches, so any lane may compute it for any candidate of the piece, at any time.
-template <class Cell>
-LLE_SEARCH_HD uint64_t successor_help(const sl::BatchView& b, const sl::RecordLayout& r, const EdgeRule& e, const Cell& cell, const uint32_t* pool,
-                                      uint64_t stride, uint64_t parent, int64_t k) {
-    return pool_help(pool, stride, r, parent) | state_edges(sl::EnvRecord{b, r, k}, r, e, cell);
+    sl::store_pool_extra(pool, stride, r, s, help_words(help));
 }
 
-// Whom the occupant of a table slot may name, as sl::Occupants, with what it takes to work out a candidate's help value.
-struct HelpOccupants {
-    sl::BatchView batch;
-    uint32_t n_tags;
-    const uint32_t* pool;
-    uint64_t stride, cap;
-    uint64_t first_state, item0;  // the piece: candidate t expands pool record first_state + (item0 + t) / n_joint
-    uint32_t n_joint;
-};
-// Is `occupant` the record `me` (a KeyWithHelp over the caller's own record)?  A tag's key words lie complete in the batch since the
-// step; its help words are not stored anywhere during the insert launch: they are worked out here, from the same inputs and with the
-// same function as by the lane that owns the candidate.  No lane waits for another.
-template <class Me, class Cell>
-LLE_SEARCH_HD bool help_occupant_is(const HelpOccupants& o, const sl::RecordLayout& r, const EdgeRule& e, const Cell& cell, uint32_t occupant, const Me& me) {
-    if (occupant & sl::TAG_BIT) {
-        const uint32_t tag = occupant & ~sl::TAG_BIT;
-        if (tag >= o.n_tags) return false;
-        const sl::EnvRecord other{o.batch, r, (int64_t)tag};
-        if (!sl::same_record(other, me, r.n_key)) return false;
-        const uint64_t parent = o.first_state + (o.item0 + tag) / o.n_joint;
-        if (parent >= o.cap) return false;
-        const uint64_t help = successor_help(o.batch, r, e, cell, o.pool, o.stride, parent, (int64_t)tag);
-        return help_lo(help) == me(r.n_key) && help_hi(help) == me(r.n_key + 1);
+struct HelpKind {
+    static constexpr int EXTRA = 2;
+    using Value = uint64_t;  // the help value
+    EdgeRule rule;
+    int32_t mode, param;
+    template <class Record, class Cell>
+    LLE_SEARCH_HD uint64_t state(const Record& rec, const sl::RecordLayout& r, const Cell& cell) const { return state_edges(rec, r, rule, cell); }
+    // The help value of a successor: its parent's, from the pool, or-ed with the edges of its own state.
+    LLE_SEARCH_HD bool successor(const uint32_t* pool, uint64_t stride, const sl::RecordLayout& r, uint64_t parent, uint64_t edges, Value* help) const {
+        *help = pool_help(pool, stride, r, parent) | edges;
+        return true;
     }
-    if (occupant >= o.cap) return false;
-    return sl::same_record(PoolKeyWithHelp{o.pool, o.stride, occupant, r.n_key, r.n_words}, me, r.n_key + 2);
-}
+    LLE_SEARCH_HD bool violates(Value help, int A) const { return lle_helpgraph_logic::violates(help, mode, param, A); }
+    LLE_SEARCH_HD bool accepts(Value help, int A) const { return lle_helpgraph_logic::accepts(help, mode, A); }
+    static LLE_SEARCH_HD sl::ExtraWords<2> words(Value help) { return help_words(help); }
+};
 
 }  // namespace lle_helpgraph_logic
 #endif  // LLE_HELPGRAPH_LOGIC_HPP

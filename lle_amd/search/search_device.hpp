@@ -3,6 +3,7 @@
 // the reset state read out of a batch and seeded into an empty pool and table, the foreign-beam table of a map, and the two device
 // functors the table code probes with.  Everything here has internal linkage: every library keeps its own error string, and no
 // symbol of one shared object can stand in for another's.  Global atomics are 32 bits wide; counters stay with the libraries.
+// search_core.hpp, beside this file, builds the single-tree search of search.hip, ../helpgraph and ../trails on top of it.
 #ifndef LLE_SEARCH_DEVICE_HPP
 #define LLE_SEARCH_DEVICE_HPP
 
@@ -133,14 +134,17 @@ int read_root(const sl::BatchView& v, const sl::RecordLayout& r, hipStream_t str
     return LLE_OK;
 }
 
-// An empty table but for the root's slot, which names state 0, and the root's words as state 0 of a pool of `stride` states.  Only
-// enqueues: the caller adds what it keeps per state and synchronises before `root` changes.
-bool seed_root(uint32_t* table, uint32_t table_mask, uint32_t* pool, uint64_t stride, const uint32_t* root, const sl::RecordLayout& r, hipStream_t stream) {
+// An empty table but for the root's slot, which names state 0, and the root's words as state 0 of a pool of `stride` states, with
+// the n_extra words `extra` of a search kind behind them (search_logic.hpp: the identity is the key words, then those).  Only
+// enqueues: the caller adds what it keeps per state and synchronises before `root` and `extra` change.
+bool seed_root(uint32_t* table, uint32_t table_mask, uint32_t* pool, uint64_t stride, const uint32_t* root, const sl::RecordLayout& r, hipStream_t stream,
+               const uint32_t* extra = nullptr, int n_extra = 0) {
     static const uint32_t zero = 0u;
-    const uint64_t h = sl::hash_record([&](int w) { return root[w]; }, r.n_key);
+    const uint64_t h = sl::hash_record([&](int w) { return w < r.n_key ? root[w] : extra[w - r.n_key]; }, r.n_key + n_extra);
     bool ok = hipMemsetAsync(table, 0xFF, ((size_t)table_mask + 1) * 4, stream) == hipSuccess &&
               hipMemcpyAsync(table + ((uint32_t)h & table_mask), &zero, 4, hipMemcpyHostToDevice, stream) == hipSuccess;
-    for (int w = 0; ok && w < r.n_words; w++) ok = hipMemcpyAsync(pool + (size_t)w * stride, &root[w], 4, hipMemcpyHostToDevice, stream) == hipSuccess;
+    for (int w = 0; ok && w < r.n_words + n_extra; w++)
+        ok = hipMemcpyAsync(pool + (size_t)w * stride, w < r.n_words ? &root[w] : &extra[w - r.n_words], 4, hipMemcpyHostToDevice, stream) == hipSuccess;
     return ok;
 }
 

@@ -2,7 +2,9 @@
 // device: the layout of a state record, its hash, one probe step of the open-addressing table, what a record means (dead agent,
 // everybody arrived, an agent on a foreign beam) and the record I/O: how a record is read out of and written into the buffers of a
 // batch (BatchView, env_word, scatter_item, copy_record), how it lies in a pool (PoolRecord) and whom a table slot names
-// (occupant_is).  ../forest/forest.hip and the steps-to-go library use the same code; search_device.hpp holds what needs HIP.
+// (occupant_is), and the records with extra words of a search KIND (ExtraWords, KeyWithExtra, Piece and the occupant comparison over
+// a kind) that ../helpgraph, ../trails and ../helpforest search with.  ../forest/forest.hip and the steps-to-go library use the same
+// code; search_device.hpp holds what needs HIP, search_core.hpp the single-tree search itself.
 // tests/hostsim/search_table.cpp drives the table code under sanitizers, tests/hostsim/record_io.cpp the record I/O.
 //
 // A RECORD is the dynamic state of one environment as 32-bit words, the identity first:
@@ -258,6 +260,103 @@ LLE_SEARCH_HD bool occupant_is(const Occupants& o, const RecordLayout& r, uint32
     }
     if (occupant >= o.cap) return false;
     return same_record(PoolRecord{o.pool, o.stride, occupant}, me, r.n_key);
+}
+
+// ---- records with extra words.  A KIND of search carries EXTRA (<= 2) more words of identity per record: the VALUE of the trajectory
+// that reached the state, hashed and compared after the key words.  The words live only in the pool, as the arrays n_words ..
+// n_words + EXTRA - 1 behind the record's: the batch has no buffer for them.  A kind says (PlainKind below; HelpKind of
+// ../helpgraph/helpgraph_logic.hpp; TrailKind of ../trails/trails_logic.hpp):
+//   EXTRA, Value      the word count, and the value as the kernels keep it per candidate between insert and commit
+//   state             the arcs of one state (`rec` its record, `cell` the map's cell table): all of it the value depends on
+//   successor         the value of a successor with those arcs whose parent is record `parent` of the pool; false: no value, the
+//                     run has no answer (the trail kind's walk ran out of budget)
+//   violates, accepts does the mode drop a trajectory with this value; may a goal state with it end a plan
+//   words             the value as ExtraWords
+template <int EXTRA>
+struct ExtraWords {
+    static_assert(EXTRA >= 0 && EXTRA <= 2, "KeyWithExtra selects among at most two words");
+    uint32_t w[EXTRA > 0 ? EXTRA : 1];
+};
+// The IDENTITY of a record: the n_key key words of `rec`, then the extra words.  What hash_record and same_record read, with n_key + EXTRA words.
+template <class Record, int EXTRA>
+struct KeyWithExtra {
+    const Record& rec;
+    int n_key;
+    ExtraWords<EXTRA> x;
+    LLE_SEARCH_HD uint32_t operator()(int w) const { return w < n_key ? rec(w) : EXTRA > 1 && w > n_key ? x.w[EXTRA > 1] : x.w[0]; }
+};
+template <int EXTRA, class Record>
+LLE_SEARCH_HD KeyWithExtra<Record, EXTRA> key_with_extra(const Record& rec, int n_key, const ExtraWords<EXTRA>& x) { return {rec, n_key, x}; }
+struct PoolKey {  // the identity of pool record s: its key words, then the words from n_words on
+    const uint32_t* pool;
+    uint64_t stride, s;
+    int n_key, n_words;
+    LLE_SEARCH_HD uint32_t operator()(int w) const { return pool[(uint64_t)(w < n_key ? w : n_words + (w - n_key)) * stride + s]; }
+};
+template <int EXTRA>
+LLE_SEARCH_HD ExtraWords<EXTRA> pool_extra(const uint32_t* pool, uint64_t stride, const RecordLayout& r, uint64_t s) {
+    ExtraWords<EXTRA> x{};
+    for (int i = 0; i < EXTRA; i++) x.w[i] = pool[(uint64_t)(r.n_words + i) * stride + s];
+    return x;
+}
+template <int EXTRA>
+LLE_SEARCH_HD void store_pool_extra(uint32_t* pool, uint64_t stride, const RecordLayout& r, uint64_t s, const ExtraWords<EXTRA>& x) {
+    for (int i = 0; i < EXTRA; i++) pool[(uint64_t)(r.n_words + i) * stride + s] = x.w[i];
+}
+
+struct PlainKind {  // the plain search: no extra words, nothing dropped
+    static constexpr int EXTRA = 0;
+    using Value = uint32_t;
+    template <class Record, class Cell> LLE_SEARCH_HD uint64_t state(const Record&, const RecordLayout&, const Cell&) const { return 0; }
+    LLE_SEARCH_HD bool successor(const uint32_t*, uint64_t, const RecordLayout&, uint64_t, uint64_t, Value* value) const { return *value = 0u, true; }
+    LLE_SEARCH_HD bool violates(Value, int) const { return false; }
+    LLE_SEARCH_HD bool accepts(Value, int) const { return true; }
+    static LLE_SEARCH_HD ExtraWords<0> words(Value) { return ExtraWords<0>{}; }
+};
+
+// The candidates of one tree in the piece in flight, and the pool they are compared with: tag t < n_tags names the candidate in
+// environment env0 + t of `batch`, work item item0 + t of the tree's level, which expands record first_state + (item0 + t) / n_joint
+// of `pool` (one pool: stride = cap = max_states; a map's segment of many: both the segment's length).  A tag at or past
+// items - item0 names nobody.  One tree alone: env0 = 0, n_tags = the piece's items, and items = item0 + n_tags or ALL_ITEMS, which
+// says the same without a second comparison in the kernel.
+constexpr uint64_t ALL_ITEMS = ~0ull;
+struct Piece {
+    BatchView batch;
+    int64_t env0;
+    uint32_t n_tags;
+    const uint32_t* pool;
+    uint64_t stride, cap;
+    uint64_t first_state, item0, items;
+    uint32_t n_joint;
+};
+// The record candidate `tag` expands (may be >= cap for a tag that names nobody: the callers check).
+LLE_SEARCH_HD uint64_t tag_parent(const Piece& o, uint32_t tag) { return o.first_state + (o.item0 + (uint64_t)tag) / o.n_joint; }
+LLE_SEARCH_HD bool tag_in_piece(const Piece& o, uint32_t tag) { return tag < o.n_tags && o.item0 + (uint64_t)tag < o.items; }
+
+// Is `occupant` the record `me` (a KeyWithExtra over the caller's own record, whose state has the arcs `arcs`)?  A tag's key words lie
+// complete in the batch since the step; its extra words are not stored anywhere during the insert launch: they are worked out here,
+// AGAIN, with the same function as by the lane that owns the candidate -- which found a value the mode keeps, or the tag would not be
+// in the table.  Equal key words mean an equal state and so equal arcs: the caller's `arcs` are applied to the other candidate's own
+// parent, which an earlier launch wrote.  No lane waits for another.
+template <class Kind, class Me>
+LLE_SEARCH_HD bool occupant_is(const Piece& o, const RecordLayout& r, const Kind& kind, uint64_t arcs, uint32_t occupant, const Me& me) {
+    if (occupant & TAG_BIT) {
+        const uint32_t tag = occupant & ~TAG_BIT;
+        if (!tag_in_piece(o, tag)) return false;
+        const EnvRecord other{o.batch, r, o.env0 + (int64_t)tag};
+        if (!same_record(other, me, r.n_key)) return false;
+        if constexpr (Kind::EXTRA > 0) {
+            const uint64_t parent = tag_parent(o, tag);
+            typename Kind::Value value;
+            if (parent >= o.cap || !kind.successor(o.pool, o.stride, r, parent, arcs, &value)) return false;
+            const ExtraWords<Kind::EXTRA> x = kind.words(value);
+            for (int i = 0; i < Kind::EXTRA; i++)
+                if (x.w[i] != me(r.n_key + i)) return false;
+        }
+        return true;
+    }
+    if (occupant >= o.cap) return false;
+    return same_record(PoolKey{o.pool, o.stride, occupant, r.n_key, r.n_words}, me, r.n_key + Kind::EXTRA);
 }
 
 // bits_lo, gems: the words w_bits and w_gems of a record.  G = the map's gems.

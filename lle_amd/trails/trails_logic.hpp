@@ -1,6 +1,6 @@
 // trails_logic.hpp -- the parts of the trail search (trails.hip, liblle_trails.so) that run the same on the host and on the device: how
-// the arcs of one state lengthen the trails of a trajectory, what no-sequence-N rejects, and the functors that append the trail word to
-// a record of ../search/search_logic.hpp.  tests/hostsim/trails_logic.cpp drives all of it under sanitizers.
+// the arcs of one state lengthen the trails of a trajectory, what no-sequence-N rejects, and TrailKind: the trail word as the extra
+// word of a record of ../search/search_logic.hpp.  tests/hostsim/trails_logic.cpp drives all of it under sanitizers.
 //
 // A TRAIL VALUE is one 32-bit word, 4 bits per agent: field a (bits 4 a .. 4 a + 3) = L[a], the length of the longest trail of help
 // edges that ends at agent a (chained, times non-decreasing, no temporal edge twice).  It is part of a record's identity: hashed and
@@ -77,69 +77,40 @@ LLE_SEARCH_HD uint32_t layer_update(uint32_t L, uint64_t edges, int N, int A, in
     return best;
 }
 
-// ---- records with a trail word
-// The IDENTITY of a record: the n_key key words of `rec`, then the trail word.  What hash_record and same_record read, with n_key + 1 words.
+// ---- records with a trail word: the trail kind of ../search/search_logic.hpp, one extra word
+// The IDENTITY of a record: the n_key key words of `rec`, then the trail word.
 template <class Record>
-struct KeyWithTrail {
-    const Record& rec;
-    int n_key;
-    uint32_t trail;
-    LLE_SEARCH_HD uint32_t operator()(int w) const { return w < n_key ? rec(w) : trail; }
-};
-template <class Record>
-LLE_SEARCH_HD KeyWithTrail<Record> key_with_trail(const Record& rec, int n_key, uint32_t trail) {
-    return KeyWithTrail<Record>{rec, n_key, trail};
+LLE_SEARCH_HD sl::KeyWithExtra<Record, 1> key_with_trail(const Record& rec, int n_key, uint32_t trail) {
+    return sl::key_with_extra(rec, n_key, sl::ExtraWords<1>{{trail}});
 }
-// Record s of a pool of `stride` records: the n_words words of search_logic.hpp's record, then the trail word at n_words.  It lives
-// only here: the batch has no buffer for it.
-LLE_SEARCH_HD uint32_t pool_trail(const uint32_t* pool, uint64_t stride, const sl::RecordLayout& r, uint64_t s) { return pool[(uint64_t)r.n_words * stride + s]; }
+// The trail word of record s of a pool of `stride` records, at n_words behind search_logic.hpp's record.
+LLE_SEARCH_HD uint32_t pool_trail(const uint32_t* pool, uint64_t stride, const sl::RecordLayout& r, uint64_t s) { return sl::pool_extra<1>(pool, stride, r, s).w[0]; }
 LLE_SEARCH_HD void store_pool_trail(uint32_t* pool, uint64_t stride, const sl::RecordLayout& r, uint64_t s, uint32_t trail) {
-    pool[(uint64_t)r.n_words * stride + s] = trail;
+    sl::store_pool_extra(pool, stride, r, s, sl::ExtraWords<1>{{trail}});
 }
-struct PoolKeyWithTrail {  // the identity of pool record s
-    const uint32_t* pool;
-    uint64_t stride, s;
-    int n_key, n_words;
-    LLE_SEARCH_HD uint32_t operator()(int w) const { return pool[(uint64_t)(w < n_key ? w : n_words) * stride + s]; }
-};
 
-// The trail value of a successor whose state has the arcs `edges` and whose parent is pool record `parent`.  Both the parent's word
-// and the state in the batch were written by earlier launches, so any lane may compute it for any candidate of the piece, at any time.
+// The trail value of a successor whose state has the arcs `edges` and whose parent is pool record `parent`.
 LLE_SEARCH_HD uint32_t successor_trail(const uint32_t* pool, uint64_t stride, const sl::RecordLayout& r, uint64_t parent, uint64_t edges, int N, int& budget) {
     return layer_update(pool_trail(pool, stride, r, parent), edges, N, r.A, budget);
 }
 
-// Whom the occupant of a table slot may name, as sl::Occupants, with what it takes to work out a candidate's trail value.
-struct TrailOccupants {
-    sl::BatchView batch;
-    uint32_t n_tags;
-    const uint32_t* pool;
-    uint64_t stride, cap;
-    uint64_t first_state, item0;  // the piece: candidate t expands pool record first_state + (item0 + t) / n_joint
-    uint32_t n_joint;
-    int32_t N;
-};
-// Is `occupant` the record `me` (a KeyWithTrail over the caller's own record, whose state has the arcs `edges`)?  A tag's key words lie
-// complete in the batch since the step; its trail word is not stored anywhere during the insert launch: it is worked out here.  Equal
-// key words mean an equal state and so equal arcs: the caller's `edges` are applied to the other candidate's parent, with the same
-// function as by the lane that owns the candidate -- which found it within the budget and below N, or the tag would not be in the
-// table.  No lane waits for another.
-template <class Me>
-LLE_SEARCH_HD bool trail_occupant_is(const TrailOccupants& o, const sl::RecordLayout& r, uint32_t occupant, const Me& me, uint64_t edges) {
-    if (occupant & sl::TAG_BIT) {
-        const uint32_t tag = occupant & ~sl::TAG_BIT;
-        if (tag >= o.n_tags) return false;
-        const sl::EnvRecord other{o.batch, r, (int64_t)tag};
-        if (!sl::same_record(other, me, r.n_key)) return false;
-        const uint64_t parent = o.first_state + (o.item0 + tag) / o.n_joint;
-        if (parent >= o.cap) return false;
+struct TrailKind {
+    static constexpr int EXTRA = 1;
+    using Value = uint32_t;  // the trail value
+    hl::EdgeRule rule;
+    int32_t N;  // no trail of N edges
+    template <class Record, class Cell>
+    LLE_SEARCH_HD uint64_t state(const Record& rec, const sl::RecordLayout& r, const Cell& cell) const { return hl::state_edges(rec, r, rule, cell); }
+    // false: the walk ran out of budget, and *trail means nothing
+    LLE_SEARCH_HD bool successor(const uint32_t* pool, uint64_t stride, const sl::RecordLayout& r, uint64_t parent, uint64_t edges, Value* trail) const {
         int budget = WALK_BUDGET;
-        const uint32_t trail = successor_trail(o.pool, o.stride, r, parent, edges, o.N, budget);
-        return budget >= 0 && trail == me(r.n_key);
+        *trail = successor_trail(pool, stride, r, parent, edges, N, budget);
+        return budget >= 0;
     }
-    if (occupant >= o.cap) return false;
-    return sl::same_record(PoolKeyWithTrail{o.pool, o.stride, occupant, r.n_key, r.n_words}, me, r.n_key + 1);
-}
+    LLE_SEARCH_HD bool violates(Value trail, int A) const { return violates_sequence(trail, N, A); }
+    LLE_SEARCH_HD bool accepts(Value, int) const { return true; }
+    static LLE_SEARCH_HD sl::ExtraWords<1> words(Value trail) { return sl::ExtraWords<1>{{trail}}; }
+};
 
 }  // namespace lle_trails_logic
 #endif  // LLE_TRAILS_LOGIC_HPP

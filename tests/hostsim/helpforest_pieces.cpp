@@ -59,16 +59,16 @@ static void ragged_lanes(unsigned seed) {
                 for (int64_t k = 0; k < n_maps * E; k++) {
                     const fl::LaneWork w = fl::lane_work(k, q, E, desc.data());
                     const fl::MapDescriptor& d = desc[(size_t)w.map];
-                    const hfl::MapPiece piece{sl::BatchView{}, fl::env_index(w.map, E, 0), (uint32_t)E, nullptr, 1000, 1000, d.first_state, q * (uint64_t)E, d.items, n_joint, 3};
+                    const sl::Piece piece{sl::BatchView{}, fl::env_index(w.map, E, 0), (uint32_t)E, nullptr, 1000, 1000, d.first_state, q * (uint64_t)E, d.items, n_joint};
                     const uint32_t tag = (uint32_t)w.local;
                     CHECK(piece.env0 + (int64_t)tag == k);  // the candidate a local tag names lies in the lane's own environment
-                    CHECK(!hfl::tag_in_piece(piece, (uint32_t)E));
+                    CHECK(!sl::tag_in_piece(piece, (uint32_t)E));
                     if (w.idle) {
-                        CHECK(!d.active || !hfl::tag_in_piece(piece, tag));
+                        CHECK(!d.active || !sl::tag_in_piece(piece, tag));
                         continue;
                     }
-                    CHECK(hfl::tag_in_piece(piece, tag));
-                    const uint64_t parent = hfl::tag_parent(piece, tag);
+                    CHECK(sl::tag_in_piece(piece, tag));
+                    const uint64_t parent = sl::tag_parent(piece, tag);
                     CHECK(parent == d.first_state + w.item / n_joint);
                     CHECK(parent >= first + (uint64_t)w.map && parent < first + (uint64_t)w.map + frontier[(size_t)w.map]);
                     lanes_checked++;
@@ -173,8 +173,8 @@ static void insert_lane(Forest& f, int kind, int mode, int param, uint64_t piece
     const sl::EnvRecord rec{f.b, r, k};
     const fl::MapDescriptor d = f.desc[(size_t)map];
     const uint32_t* seg = f.segment(map);
-    const hfl::MapPiece who{f.b, fl::env_index(map, f.E, 0), (uint32_t)f.E, seg, f.cap, f.cap, d.first_state, piece * (uint64_t)f.E, d.items, f.n_joint, param};
-    const uint64_t parent = hfl::tag_parent(who, local);
+    const sl::Piece who{f.b, fl::env_index(map, f.E, 0), (uint32_t)f.E, seg, f.cap, f.cap, d.first_state, piece * (uint64_t)f.E, d.items, f.n_joint};
+    const uint64_t parent = sl::tag_parent(who, local);
     const uint32_t* cells = f.map_cells(map);
     auto cell = [&](int c) { return cells[c]; };
     const hl::EdgeRule& rule = f.rules[map];
@@ -182,28 +182,31 @@ static void insert_lane(Forest& f, int kind, int mode, int param, uint64_t piece
     int64_t slot;
     uint64_t extra;
     if (kind == hfl::KIND_HELP) {
-        const uint64_t help = hl::successor_help(f.b, r, rule, cell, seg, f.cap, parent, k);
+        const hl::HelpKind help_kind{rule, mode, param};
+        const uint64_t edges = help_kind.state(rec, r, cell);
+        uint64_t help = 0;
+        CHECK(help_kind.successor(seg, f.cap, r, parent, edges, &help));
         if (hl::violates(help, mode, param, r.A)) return;
         const auto me = hl::key_with_help(rec, r.n_key, help);
         auto same_as = [&](uint32_t occupant) {
-            const bool same = hfl::help_occupant_is(who, r, rule, cell, occupant, me);
+            const bool same = sl::occupant_is(who, r, help_kind, edges, occupant, me);
             if (same) (occupant & sl::TAG_BIT ? tag_matches : pool_matches)++;
             return same;
         };
         slot = sl::table_insert(table, (uint32_t)(f.slots - 1), sl::hash_record(me, r.n_key + 2), sl::TAG_BIT | local, HostLoad{}, HostCas{}, same_as);
         extra = help;
     } else {
-        const uint64_t edges = hl::state_edges(rec, r, rule, cell);
-        int budget = tl::WALK_BUDGET;
-        const uint32_t trail = tl::successor_trail(seg, f.cap, r, parent, edges, param, budget);
-        if (budget < 0) {
+        const tl::TrailKind trail_kind{rule, param};
+        const uint64_t edges = trail_kind.state(rec, r, cell);
+        uint32_t trail = 0;
+        if (!trail_kind.successor(seg, f.cap, r, parent, edges, &trail)) {
             counters[hfl::CNT_DENSE]++;
             return;
         }
         if (tl::violates_sequence(trail, param, r.A)) return;
         const auto me = tl::key_with_trail(rec, r.n_key, trail);
         auto same_as = [&](uint32_t occupant) {
-            const bool same = hfl::trail_occupant_is(who, r, occupant, me, edges);
+            const bool same = sl::occupant_is(who, r, trail_kind, edges, occupant, me);
             if (same) (occupant & sl::TAG_BIT ? tag_matches : pool_matches)++;
             return same;
         };

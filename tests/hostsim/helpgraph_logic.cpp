@@ -7,7 +7,7 @@
 //   * the table code of search_logic.hpp with help words in the identity, the way hg_insert and hg_commit use it: candidates that differ
 //     ONLY in a help word -- tag against tag inside a piece, and tag against pool across pieces -- must both be stored; candidates that
 //     are equal, help words included, must be stored exactly once.  A candidate's help words are never kept during the insert: the
-//     comparing side works them out again from the candidate's batch record and its parent's pool record (help_occupant_is).
+//     comparing side works them out again from its own edges (equal key words, equal edges) and the candidate's parent's pool record (sl::occupant_is over hl::HelpKind).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -236,15 +236,17 @@ int main(int argc, char** argv) {
                 fb.gems[(size_t)k] = v & 1u;
                 for (int w = 0; w < Lw; w++) fb.beams[(size_t)k * Lw + w] = 7u;
             }
-            const hl::HelpOccupants who{fb.v, (uint32_t)n, pool.data(), cap, cap, first_state, item0, n_joint};
+            const sl::Piece who{fb.v, 0, (uint32_t)n, pool.data(), cap, cap, first_state, item0, item0 + (uint64_t)n, n_joint};
+            const hl::HelpKind kind{rule, hl::STANDARD, 0};
             std::vector<int64_t> win((size_t)n, -1);
             std::vector<uint64_t> help((size_t)n, 0);
             for (int k = 0; k < n; k++) {
                 const sl::EnvRecord rec{fb.v, r, k};
                 const uint64_t parent = first_state + (item0 + (uint64_t)k) / n_joint;
-                help[(size_t)k] = hl::successor_help(fb.v, r, rule, cell, pool.data(), cap, parent, k);
+                const uint64_t edges = kind.state(rec, r, cell);
+                CHECK(kind.successor(pool.data(), cap, r, parent, edges, &help[(size_t)k]));
                 const auto me = hl::key_with_help(rec, r.n_key, help[(size_t)k]);
-                auto same_as = [&](uint32_t occupant) { return hl::help_occupant_is(who, r, rule, cell, occupant, me); };
+                auto same_as = [&](uint32_t occupant) { return sl::occupant_is(who, r, kind, edges, occupant, me); };
                 const int64_t slot = sl::table_insert(table.data(), slots - 1, sl::hash_record(me, r.n_key + 2), sl::TAG_BIT | (uint32_t)k, load, cas, same_as);
                 std::vector<uint32_t> id;
                 for (int w = 0; w < r.n_key + 2; w++) id.push_back(me(w));
@@ -294,13 +296,17 @@ int main(int argc, char** argv) {
         for (int piece = 0; piece < 2; piece++) {
             FakeBatch fb(3, A, 1);  // three equal states
             for (int k = 0; k < 3; k++) fb.bits[(size_t)k] = 3u | (uint64_t)3u << 32;
-            const hl::HelpOccupants who{fb.v, 3u, pool.data(), cap, cap, 0, 0, n_joint};
+            const sl::Piece who{fb.v, 0, 3u, pool.data(), cap, cap, 0, 0, sl::ALL_ITEMS, n_joint};
+            const hl::HelpKind kind{rule, hl::STANDARD, 0};
             int winners = 0;
             int64_t win[3];
             for (int k = 0; k < 3; k++) {
                 const sl::EnvRecord rec{fb.v, r, k};
-                const auto me = hl::key_with_help(rec, r.n_key, hl::successor_help(fb.v, r, rule, cell, pool.data(), cap, (uint64_t)k, k));
-                auto same_as = [&](uint32_t occupant) { return hl::help_occupant_is(who, r, rule, cell, occupant, me); };
+                const uint64_t edges = kind.state(rec, r, cell);
+                uint64_t help = 0;
+                CHECK(kind.successor(pool.data(), cap, r, (uint64_t)k, edges, &help));
+                const auto me = hl::key_with_help(rec, r.n_key, help);
+                auto same_as = [&](uint32_t occupant) { return sl::occupant_is(who, r, kind, edges, occupant, me); };
                 win[k] = sl::table_insert(table.data(), slots - 1, 5u /* one hash for all: they meet */, sl::TAG_BIT | (uint32_t)k, load, cas, same_as);
                 winners += win[k] >= 0;
             }

@@ -11,7 +11,7 @@
 //     what the brute force gives or report dense -- never a wrong answer; a state of at most 6 arcs is never dense
 //   * the table code of search_logic.hpp with the trail word in the identity, the way tr_insert and tr_commit use it: candidates that
 //     differ ONLY in the trail word are both stored, candidates equal in it exactly once; a candidate's trail word is never kept during
-//     the insert: the comparing side works it out again from its own arcs and the other parent's pool record (trail_occupant_is)
+//     the insert: the comparing side works it out again from its own arcs and the other parent's pool record (sl::occupant_is over tl::TrailKind)
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -283,15 +283,15 @@ int main(int argc, char** argv) {
         for (int piece = 0; piece < 2; piece++) {
             FakeBatch fb(3, A);  // three equal states
             for (int k = 0; k < 3; k++) fb.bits[(size_t)k] = 3u | (uint64_t)3u << 32;
-            const tl::TrailOccupants who{fb.v, 3u, pool.data(), cap, cap, 0, 0, n_joint, 5};
+            const sl::Piece who{fb.v, 0, 3u, pool.data(), cap, cap, 0, 0, 3, n_joint};
+            const tl::TrailKind kind{{}, 5};  // (the arcs are given: no edge rule is read)
             int64_t win[3];
             uint32_t trail[3];
             for (int k = 0; k < 3; k++) {
                 const sl::EnvRecord rec{fb.v, r, k};
-                int budget = tl::WALK_BUDGET;
-                trail[k] = tl::successor_trail(pool.data(), cap, r, (uint64_t)k, edges, 5, budget);
+                CHECK(kind.successor(pool.data(), cap, r, (uint64_t)k, edges, &trail[k]));
                 const auto me = tl::key_with_trail(rec, r.n_key, trail[k]);
-                auto same_as = [&](uint32_t occupant) { return tl::trail_occupant_is(who, r, occupant, me, edges); };
+                auto same_as = [&](uint32_t occupant) { return sl::occupant_is(who, r, kind, edges, occupant, me); };
                 win[k] = sl::table_insert(table.data(), slots - 1, 5u /* one hash for all: they meet */, sl::TAG_BIT | (uint32_t)k, load, cas, same_as);
                 stored += win[k] >= 0;
                 duplicates += win[k] == sl::INSERT_DUPLICATE;

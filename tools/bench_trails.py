@@ -44,6 +44,8 @@ def main():
     maps = dict({c["name"]: c["map"] for c in cases["catalogue"] if "map" in c}, **cases["maps"])
     rows, standard_cache = [], {}
     for s in cases["searches"]:
+        if "changes" in s:  # a search on a changed world (tests/test_gpu_trails_edges.py): the tests' concern, not timed here, as bench_helpgraph.py
+            continue
         key = (s["map"], s["t_max"], s["collect_gems"])
         if key not in standard_cache:
             standard = HelpGraphSolver(maps[s["map"]], s["t_max"], chunk=args.chunk)
