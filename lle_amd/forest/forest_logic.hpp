@@ -21,6 +21,8 @@ constexpr int64_t MAX_LANES = (int64_t)1 << 30;                                /
 constexpr uint64_t MAX_TABLE_SLOTS = (uint64_t)1 << 31;                        // per segment: no slot number is SLOT_EMPTY
 constexpr int N_COUNTERS = 8;
 enum { CNT_STATES = 0, CNT_EXPANDED, CNT_GOAL, CNT_OVERFLOW, CNT_STEP_ERRORS };
+constexpr int CNT_DENSE = 5;  // work items whose walk ran out of budget: written and read only where the kind has a walk (the trail kind)
+static_assert(CNT_DENSE > CNT_STEP_ERRORS && CNT_DENSE < N_COUNTERS, "the slot is taken");
 constexpr uint64_t NO_GOAL = ~(uint64_t)0;
 
 // What the kernels of a level know of one map (one async copy per level).
@@ -70,6 +72,8 @@ LLE_SEARCH_HD uint64_t level_items(const MapDescriptor* desc, int64_t n_maps) {
 LLE_SEARCH_HD int64_t env_index(int64_t map, int64_t E, int64_t local) { return map * E + local; }
 // word w of local state s: pool[(map * n_words + w) * cap + s] -- structure of arrays inside the segment, as in search.hip
 LLE_SEARCH_HD uint64_t pool_index(int64_t map, int n_words, int w, uint64_t cap, uint64_t s) { return ((uint64_t)map * (uint64_t)n_words + (uint64_t)w) * cap + s; }
+// a map's segment of the pool: seg_words arrays of `cap` words (the record's n_words, then the library's extra words)
+LLE_SEARCH_HD uint64_t pool_segment_offset(int64_t map, int seg_words, uint64_t cap) { return (uint64_t)map * (uint64_t)seg_words * cap; }
 LLE_SEARCH_HD uint64_t state_index(int64_t map, uint64_t cap, uint64_t s) { return (uint64_t)map * cap + s; }      // parent, action
 LLE_SEARCH_HD uint64_t table_base(int64_t map, uint64_t slots) { return (uint64_t)map * slots; }
 LLE_SEARCH_HD uint64_t counter_index(int64_t map, int which) { return (uint64_t)map * N_COUNTERS + (uint64_t)which; }
@@ -77,13 +81,13 @@ LLE_SEARCH_HD uint64_t foreign_base(int64_t map, int H, int W) { return (uint64_
 using lle_search_logic::table_slots;  // (cap, E): a map's table segment is the single search's table with chunk = E
 
 // ---- the host's view of one map during a run
-enum { FATE_CONTINUE = 0, FATE_SOLVED, FATE_EMPTY, FATE_CAPACITY, FATE_STEP_ERROR };
+enum { FATE_CONTINUE = 0, FATE_SOLVED, FATE_EMPTY, FATE_CAPACITY, FATE_STEP_ERROR, FATE_DENSE };
 
 struct MapProgress {
     uint64_t level_start, level_end;  // the frontier: local pool indices [level_start, level_end)
     uint64_t expanded_before;
     int32_t active;
-    int32_t status;         // 0, or the capacity status
+    int32_t status;         // 0, the capacity status or the dense status
     int32_t length;         // -1: no plan (yet)
     int32_t depth_reached;
     int64_t n_states;
@@ -113,14 +117,23 @@ LLE_SEARCH_HD MapDescriptor level_descriptor(const MapProgress& p, uint32_t n_jo
 }
 
 // After level `depth` (1-based) of an active map: read its counters, move its frontier on and say what became of it.
-// *frontier_new / *expanded_new: the level's entries of the per-depth statistics (not written for FATE_CAPACITY / FATE_STEP_ERROR).
-LLE_SEARCH_HD int advance(MapProgress& p, const uint64_t* counters, uint64_t cap, int depth, int capacity_status, int64_t* frontier_new, int64_t* expanded_new) {
+// *frontier_new / *expanded_new: the level's entries of the per-depth statistics (written for no fate that ends without an answer).
+// dense_status: 0 when the kind has no walk -- the dense counter is not read then.  Otherwise a map whose walk ran out of budget ends
+// with it, no answer and n_states 1, like a single trail search.  Capacity goes first: a map over capacity AND dense reports capacity.
+LLE_SEARCH_HD int advance(MapProgress& p, const uint64_t* counters, uint64_t cap, int depth, int capacity_status, int dense_status, int64_t* frontier_new,
+                          int64_t* expanded_new) {
     p.depth_reached = depth;
     if (counters[CNT_OVERFLOW] != 0u || counters[CNT_STATES] > cap) {
         p.active = 0;
         p.status = capacity_status;
         p.n_states = (int64_t)cap;
         return FATE_CAPACITY;
+    }
+    if (dense_status != 0 && counters[CNT_DENSE] != 0u) {
+        p.active = 0;
+        p.status = dense_status;
+        p.n_states = 1;
+        return FATE_DENSE;
     }
     if (counters[CNT_STEP_ERRORS] != 0u) {
         p.active = 0;

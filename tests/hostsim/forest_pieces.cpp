@@ -147,7 +147,7 @@ static void fates() {
     // level 1: 9 available joint actions, 4 new states
     c[fl::CNT_STATES] = 5;
     c[fl::CNT_EXPANDED] = 9;
-    CHECK(fl::advance(p, c, 100, 1, CAPACITY, &fr, &ex) == fl::FATE_CONTINUE && fr == 4 && ex == 9 && p.active);
+    CHECK(fl::advance(p, c, 100, 1, CAPACITY, 0, &fr, &ex) == fl::FATE_CONTINUE && fr == 4 && ex == 9 && p.active);
     CHECK(p.level_start == 1 && p.level_end == 5 && p.n_states == 5 && p.depth_reached == 1);
     CHECK(fl::level_descriptor(p, 25).first_state == 1 && fl::level_descriptor(p, 25).items == 100);
     // level 2: a goal among 7 new states -- the level is whole, the map stops
@@ -155,32 +155,38 @@ static void fates() {
     c[fl::CNT_EXPANDED] = 40;
     c[fl::CNT_GOAL] = 8;
     fl::MapProgress solved = p;
-    CHECK(fl::advance(solved, c, 100, 2, CAPACITY, &fr, &ex) == fl::FATE_SOLVED && fr == 7 && ex == 31);
+    CHECK(fl::advance(solved, c, 100, 2, CAPACITY, 0, &fr, &ex) == fl::FATE_SOLVED && fr == 7 && ex == 31);
     CHECK(!solved.active && solved.length == 2 && solved.goal == 8 && solved.n_states == 12 && solved.status == 0);
     CHECK(fl::level_descriptor(solved, 25).active == 0 && fl::level_descriptor(solved, 25).items == 0);
     // level 2 otherwise: nothing new -- the frontier ran empty at depth 2
     c[fl::CNT_STATES] = 5;
     c[fl::CNT_GOAL] = fl::NO_GOAL;
     fl::MapProgress empty = p;
-    CHECK(fl::advance(empty, c, 100, 2, CAPACITY, &fr, &ex) == fl::FATE_EMPTY && fr == 0 && ex == 31 && !empty.active && empty.length == -1);
+    CHECK(fl::advance(empty, c, 100, 2, CAPACITY, 0, &fr, &ex) == fl::FATE_EMPTY && fr == 0 && ex == 31 && !empty.active && empty.length == -1);
     CHECK(empty.depth_reached == 2 && empty.n_states == 5);
     // the pool overflowed: by the flag, or by a counter past cap (the flag's launch may be the level's last)
     c[fl::CNT_STATES] = 12;
     c[fl::CNT_OVERFLOW] = 1;
     fl::MapProgress over = p;
-    CHECK(fl::advance(over, c, 100, 2, CAPACITY, &fr, &ex) == fl::FATE_CAPACITY && !over.active && over.status == CAPACITY && over.length == -1 && over.n_states == 100);
+    CHECK(fl::advance(over, c, 100, 2, CAPACITY, 0, &fr, &ex) == fl::FATE_CAPACITY && !over.active && over.status == CAPACITY && over.length == -1 && over.n_states == 100);
     c[fl::CNT_OVERFLOW] = 0;
     c[fl::CNT_STATES] = 101;
     c[fl::CNT_GOAL] = 3;  // a goal beside an overflow is no answer
     over = p;
-    CHECK(fl::advance(over, c, 100, 2, CAPACITY, &fr, &ex) == fl::FATE_CAPACITY && over.length == -1);
+    CHECK(fl::advance(over, c, 100, 2, CAPACITY, 0, &fr, &ex) == fl::FATE_CAPACITY && over.length == -1);
     c[fl::CNT_STATES] = 100;  // exactly full is no overflow
     over = p;
-    CHECK(fl::advance(over, c, 100, 2, CAPACITY, &fr, &ex) == fl::FATE_SOLVED && over.n_states == 100);
+    CHECK(fl::advance(over, c, 100, 2, CAPACITY, 0, &fr, &ex) == fl::FATE_SOLVED && over.n_states == 100);
     c[fl::CNT_GOAL] = fl::NO_GOAL;
     c[fl::CNT_STEP_ERRORS] = 2;
     fl::MapProgress refused = p;
-    CHECK(fl::advance(refused, c, 100, 2, CAPACITY, &fr, &ex) == fl::FATE_STEP_ERROR && !refused.active);
+    CHECK(fl::advance(refused, c, 100, 2, CAPACITY, 0, &fr, &ex) == fl::FATE_STEP_ERROR && !refused.active);
+    // a kind without a walk (dense_status 0) does not read the dense counter, whatever lies there
+    c[fl::CNT_STEP_ERRORS] = 0;
+    c[fl::CNT_DENSE] = 7;
+    fl::MapProgress plain = p;
+    CHECK(fl::advance(plain, c, 100, 2, CAPACITY, 0, &fr, &ex) == fl::FATE_CONTINUE && plain.status == 0 && plain.n_states == 100 && fr == 95);
+    c[fl::CNT_DENSE] = 0;
     // counters near 2^31 and past it
     c[fl::CNT_STEP_ERRORS] = 0;
     fl::MapProgress big = fl::fresh_progress(true);
@@ -189,7 +195,7 @@ static void fates() {
     big.expanded_before = ((uint64_t)1 << 31) - 1;
     c[fl::CNT_STATES] = (uint64_t)1 << 30;
     c[fl::CNT_EXPANDED] = ((uint64_t)1 << 44) + 5;
-    CHECK(fl::advance(big, c, (uint64_t)1 << 30, 9, CAPACITY, &fr, &ex) == fl::FATE_CONTINUE && fr == 3);
+    CHECK(fl::advance(big, c, (uint64_t)1 << 30, 9, CAPACITY, 0, &fr, &ex) == fl::FATE_CONTINUE && fr == 3);
     CHECK(ex == (int64_t)(((uint64_t)1 << 44) + 5 - (((uint64_t)1 << 31) - 1)) && big.level_start == ((uint64_t)1 << 30) - 3);
 }
 

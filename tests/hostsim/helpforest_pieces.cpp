@@ -114,7 +114,7 @@ struct Forest {
         gems.assign(lanes, 0);
         beams.assign(lanes, 0);
         win.assign(lanes, sl::SLOT_EMPTY);
-        pool.assign((size_t)hfl::pool_segment_offset(N_MAPS, r.n_words, cap), 0xDEADBEEFu);
+        pool.assign((size_t)fl::pool_segment_offset(N_MAPS, r.n_words + hfl::EXTRA_WORDS, cap), 0xDEADBEEFu);
         parent.assign((size_t)N_MAPS * cap, 0);
         table.assign((size_t)N_MAPS * slots, sl::SLOT_EMPTY);
         counters.assign((size_t)N_MAPS * fl::N_COUNTERS, 0);
@@ -149,7 +149,7 @@ struct Forest {
         b.avail_stride = 2;
         b.act_stride = 2;
     }
-    uint32_t* segment(int64_t m) { return pool.data() + hfl::pool_segment_offset(m, r.n_words, cap); }
+    uint32_t* segment(int64_t m) { return pool.data() + fl::pool_segment_offset(m, r.n_words + hfl::EXTRA_WORDS, cap); }
     const uint32_t* map_cells(int64_t m) const { return cells.data() + (size_t)m * H * W; }
     // what the "step" makes of joint action `code`: agent 0 in column 1, agent 1 in column 2, each in row 1 or 2 -- four states per map
     void write_env(int64_t k, uint32_t code) {
@@ -200,7 +200,7 @@ static void insert_lane(Forest& f, int kind, int mode, int param, uint64_t piece
         const uint64_t edges = trail_kind.state(rec, r, cell);
         uint32_t trail = 0;
         if (!trail_kind.successor(seg, f.cap, r, parent, edges, &trail)) {
-            counters[hfl::CNT_DENSE]++;
+            counters[fl::CNT_DENSE]++;
             return;
         }
         if (tl::violates_sequence(trail, param, r.A)) return;
@@ -343,35 +343,35 @@ static void fates() {
         c[m][fl::CNT_EXPANDED] = 9;
         c[m][fl::CNT_GOAL] = fl::NO_GOAL;
     }
-    c[1][hfl::CNT_DENSE] = 3;  // the middle map's walk ran out of budget
+    c[1][fl::CNT_DENSE] = 3;  // the middle map's walk ran out of budget
     int64_t fr[3] = {-1, -1, -1}, ex[3] = {-1, -1, -1};
-    const int fate0 = hfl::advance(p[0], c[0], 100, 1, CAPACITY, DENSE, &fr[0], &ex[0]);
-    const int fate1 = hfl::advance(p[1], c[1], 100, 1, CAPACITY, DENSE, &fr[1], &ex[1]);
-    const int fate2 = hfl::advance(p[2], c[2], 100, 1, CAPACITY, DENSE, &fr[2], &ex[2]);
-    CHECK(fate0 == fl::FATE_CONTINUE && fate2 == fl::FATE_CONTINUE && fate1 == hfl::FATE_DENSE);
+    const int fate0 = fl::advance(p[0], c[0], 100, 1, CAPACITY, DENSE, &fr[0], &ex[0]);
+    const int fate1 = fl::advance(p[1], c[1], 100, 1, CAPACITY, DENSE, &fr[1], &ex[1]);
+    const int fate2 = fl::advance(p[2], c[2], 100, 1, CAPACITY, DENSE, &fr[2], &ex[2]);
+    CHECK(fate0 == fl::FATE_CONTINUE && fate2 == fl::FATE_CONTINUE && fate1 == fl::FATE_DENSE);
     CHECK(!p[1].active && p[1].status == DENSE && p[1].length == -1 && p[1].n_states == 1 && p[1].depth_reached == 1 && fr[1] == -1);
     for (int m : {0, 2}) CHECK(p[m].active && p[m].status == 0 && p[m].n_states == 5 && fr[m] == 4 && ex[m] == 9 && p[m].level_start == 1 && p[m].level_end == 5);
     // capacity goes before dense, and isolates the same way
     fl::MapProgress q = fl::fresh_progress(true);
     c[1][fl::CNT_OVERFLOW] = 1;
-    CHECK(hfl::advance(q, c[1], 100, 1, CAPACITY, DENSE, &fr[1], &ex[1]) == fl::FATE_CAPACITY && q.status == CAPACITY && q.n_states == 100);
+    CHECK(fl::advance(q, c[1], 100, 1, CAPACITY, DENSE, &fr[1], &ex[1]) == fl::FATE_CAPACITY && q.status == CAPACITY && q.n_states == 100);
     c[1][fl::CNT_OVERFLOW] = 0;
     c[1][fl::CNT_STATES] = 101;
     q = fl::fresh_progress(true);
-    CHECK(hfl::advance(q, c[1], 100, 1, CAPACITY, DENSE, &fr[1], &ex[1]) == fl::FATE_CAPACITY);
+    CHECK(fl::advance(q, c[1], 100, 1, CAPACITY, DENSE, &fr[1], &ex[1]) == fl::FATE_CAPACITY);
     // a goal beside a dense item is no answer
     c[1][fl::CNT_STATES] = 7;
     c[1][fl::CNT_GOAL] = 6;
     q = fl::fresh_progress(true);
-    CHECK(hfl::advance(q, c[1], 100, 1, CAPACITY, DENSE, &fr[1], &ex[1]) == hfl::FATE_DENSE && q.length == -1);
-    c[1][hfl::CNT_DENSE] = 0;
+    CHECK(fl::advance(q, c[1], 100, 1, CAPACITY, DENSE, &fr[1], &ex[1]) == fl::FATE_DENSE && q.length == -1);
+    c[1][fl::CNT_DENSE] = 0;
     q = fl::fresh_progress(true);
-    CHECK(hfl::advance(q, c[1], 100, 1, CAPACITY, DENSE, &fr[1], &ex[1]) == fl::FATE_SOLVED && q.length == 1 && q.goal == 6);
+    CHECK(fl::advance(q, c[1], 100, 1, CAPACITY, DENSE, &fr[1], &ex[1]) == fl::FATE_SOLVED && q.length == 1 && q.goal == 6);
     // a map the mask leaves out
     const fl::MapProgress s = hfl::skipped_progress();
     CHECK(!s.active && s.length == -1 && s.n_states == 0 && s.depth_reached == 0 && s.status == 0 && fl::level_descriptor(s, 25).items == 0);
     CHECK(hfl::kind_of(hfl::NO_SEQUENCE) == hfl::KIND_TRAIL && hfl::kind_of(hl::NO_ASYMMETRIC) == hfl::KIND_HELP && hfl::NO_SEQUENCE == 6);
-    CHECK(hfl::pool_segment_offset(255, 40, (uint64_t)1 << 30) == (uint64_t)255 * 42 * ((uint64_t)1 << 30));
+    CHECK(fl::pool_segment_offset(255, 40 + hfl::EXTRA_WORDS, (uint64_t)1 << 30) == (uint64_t)255 * 42 * ((uint64_t)1 << 30));
 }
 
 int main(int argc, char** argv) {

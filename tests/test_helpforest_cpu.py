@@ -66,7 +66,8 @@ def test_library_exports_sizes_and_constants():
     assert helpforest.LLE_HELPFOREST_NO_SEQUENCE == len(helpgraph._NATIVE) == 6 and solver.LLE_SEARCH_CAPACITY == helpgraph.LLE_HELPGRAPH_CAPACITY
     # what the library static_asserts against the logic headers
     logic = open(os.path.join(ROOT, "lle_amd", "helpforest", "helpforest_logic.hpp")).read()
-    assert "NO_SEQUENCE = hl::N_MODES" in logic and "CNT_DENSE = 5" in logic and "LLE_HELPFOREST_NO_SEQUENCE == hfl::NO_SEQUENCE" in source
+    forest_logic = open(os.path.join(ROOT, "lle_amd", "forest", "forest_logic.hpp")).read()  # (the dense counter lies beside the forest's others)
+    assert "NO_SEQUENCE = hl::N_MODES" in logic and "CNT_DENSE = 5" in forest_logic and "LLE_HELPFOREST_NO_SEQUENCE == hfl::NO_SEQUENCE" in source
     assert sorted(helpforest.compiled_kernels()) == sorted(helpforest.KERNELS) and len(helpforest.KERNELS) == 9
     assert helpforest.launched_kernels() == []
 
