@@ -24,6 +24,9 @@ def __getattr__(name):
     if name == "CooperationTracker":
         from .cooperation import CooperationTracker
         return CooperationTracker
+    if name == "TemporalCooperationTracker":  # (is_sequential / is_mutual for a whole batch, liblle_cooptrails.so)
+        from .cooptrails import TemporalCooperationTracker
+        return TemporalCooperationTracker
     if name in ("Solver", "solve", "SolveMode", "SolverCapacityError"):  # (lle.solver: the exact shortest-plan search, liblle_search.so)
         from . import solver
         return getattr(solver, name)
@@ -61,4 +64,4 @@ __all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorl
            "ObservationType", "ParsingError", "PartialGenerator", "PotentialShapedLLE", "SingleObjective", "SolveMode", "Solver", "SolverCapacityError", "StateGenerator", "World", "WorldCharacterizer", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "solve", "types", "world",
            "ForestSolver", "ForestResult", "solve_many", "characterize_many", "Constraint", "WorldFilter", "generate_n",
            "OptimalPolicy", "PolicyCapacityError", "HelpGraphSolver", "HelpGraphCharacterizer", "TrailSolver", "TrailCharacterizer",
-           "HelpForestSolver", "HelpForestResult", "ManyHelpCharacterization"]
+           "HelpForestSolver", "HelpForestResult", "ManyHelpCharacterization", "TemporalCooperationTracker"]
