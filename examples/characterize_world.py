@@ -20,6 +20,15 @@ S2   .   . . . @
  @   @   X X X L1W
 """
 
+PAPER_INTERDEPENDENT_3 = """
+ @   S0   @ L2S   S1 @
+L0E  .    .   .   .  @
+ @   .    @   X   .  @
+ @   .    @   .   X L1W
+ @   .    @   .   .  @
+ @   .    .   X   S2 @
+"""
+
 
 def main():
     from lle_amd import TrailCharacterizer, World
@@ -46,6 +55,12 @@ def main():
                        ("without a sequence of 3", c.compute_shortest_path_without_sequence(3))):
         print(f"  shortest plan {name:<26}{'none' if path is None else len(path)}")
     c._solver.free()
+    # closed trails over exactly three agents: the reference's headline layout, under CycleCharacterizer
+    from lle_amd import CycleCharacterizer
+    cc = CycleCharacterizer(World(PAPER_INTERDEPENDENT_3), t_max)
+    print(f"paper-interdependent-3, t_max = {t_max}: is_interdependent(2) {cc.is_interdependent(2)}, is_interdependent(3) {cc.is_interdependent(3)}, "
+          f"shortest plan without a closed trail over three agents: {'none' if cc.compute_shortest_non_interdependent_path(3) is None else len(cc.compute_shortest_non_interdependent_path(3))}")
+    cc._solver.free()
 
 
 if __name__ == "__main__":

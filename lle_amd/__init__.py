@@ -39,6 +39,9 @@ def __getattr__(name):
     if name in ("TrailSolver", "TrailCharacterizer"):  # (no-sequence-N: trails of help events in time order, liblle_trails.so)
         from . import trails
         return getattr(trails, name)
+    if name in ("CycleSolver", "CycleCharacterizer"):  # (no-interdependence-N: closed trails over exactly N agents, liblle_cycles.so)
+        from . import cycles
+        return getattr(cycles, name)
     if name in ("ForestSolver", "ForestResult", "solve_many", "characterize_many"):  # (the same search over many maps at once, liblle_forest.so)
         from . import forest
         return getattr(forest, name)
@@ -64,4 +67,5 @@ __all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorl
            "ObservationType", "ParsingError", "PartialGenerator", "PotentialShapedLLE", "SingleObjective", "SolveMode", "Solver", "SolverCapacityError", "StateGenerator", "World", "WorldCharacterizer", "WorldEvent", "WorldState", "__version__", "exceptions", "tiles", "solve", "types", "world",
            "ForestSolver", "ForestResult", "solve_many", "characterize_many", "Constraint", "WorldFilter", "generate_n",
            "OptimalPolicy", "PolicyCapacityError", "HelpGraphSolver", "HelpGraphCharacterizer", "TrailSolver", "TrailCharacterizer",
-           "HelpForestSolver", "HelpForestResult", "ManyHelpCharacterization", "TemporalCooperationTracker"]
+           "HelpForestSolver", "HelpForestResult", "ManyHelpCharacterization", "TemporalCooperationTracker",
+           "CycleSolver", "CycleCharacterizer"]

@@ -210,7 +210,7 @@ class Divergent(Predicate):
 @dataclass(frozen=True)
 class Interdependent(Predicate):
     """A closed chain of help over `order` agents is required (solve mode 'no-interdependence-N': order 2 is 'no-mutual', answered like
-    `Asymmetric`; N >= 3 is not built)."""
+    `Asymmetric`; N >= 3 is answered by lle_amd.CycleCharacterizer alone, one world at a time: pass it as `characterizer=`)."""
     order: int = 2
 
     def __post_init__(self):
@@ -335,7 +335,7 @@ class Constraint:
     def is_satisfied_by(self, world, *, characterizer=WorldCharacterizer, **solver_options):
         """Whether `world` satisfies the constraint: one `characterizer` (`solver_options` go to its Solver).  WorldCharacterizer
         answers Solvable / Independent / Cooperative; lle_amd.HelpGraphCharacterizer also Asymmetric, Convergent, Divergent and
-        Interdependent(2); lle_amd.TrailCharacterizer also Sequential(N)."""
+        Interdependent(2); lle_amd.TrailCharacterizer also Sequential(N); lle_amd.CycleCharacterizer also Interdependent(N) for N >= 3."""
         return self._accepts(characterizer(world, self.t_max, **solver_options))
 
     def satisfied_by_many(self, worlds, *, characterizer=None, **options):
@@ -344,8 +344,9 @@ class Constraint:
         plain forest (`lle_amd.forest.characterize_many`), which answers Solvable / Independent / Cooperative.
         lle_amd.HelpGraphCharacterizer or lle_amd.TrailCharacterizer: the help forest (`lle_amd.helpforest.characterize_many`),
         which also answers Asymmetric, Convergent, Divergent, Interdependent(2) and -- under TrailCharacterizer -- Sequential(N); every
-        atom costs at most one forest run per shape, made when the first world needs it.  Any other class: one such characterizer
-        per world (then `options` go to its Solver)."""
+        atom costs at most one forest run per shape, made when the first world needs it.  Any other class -- lle_amd.CycleCharacterizer
+        for Interdependent(N >= 3), which the help forest does not answer -- : one such characterizer per world (then `options` go
+        to its Solver)."""
         worlds = list(worlds)
         if characterizer is None:
             from .forest import characterize_many

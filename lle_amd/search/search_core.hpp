@@ -1,6 +1,7 @@
-// search_core.hpp -- the single-tree search that search.hip, ../helpgraph/helpgraph.hip and ../trails/trails.hip share: ONE breadth-first
+// search_core.hpp -- the single-tree search that search.hip, ../helpgraph/helpgraph.hip, ../trails/trails.hip and ../cycles/cycles.hip share: ONE breadth-first
 // tree over the records of one map, with the extra words of a KIND behind them (search_logic.hpp: PlainKind, none; helpgraph_logic.hpp:
-// HelpKind, two; trails_logic.hpp: TrailKind, one).  Here are the shared kernel parameters and counters, the device bodies of the
+// HelpKind, two; trails_logic.hpp: TrailKind, one; ../cycles/cycles_logic.hpp:
+// CycleKind, three or twenty-one).  Here are the shared kernel parameters and counters, the device bodies of the
 // expand, insert and commit kernels, the handle with its device buffers, the two halves of a create, the seeding of record 0, the
 // level loop with its counter read-back, the plan walk, and plan / stats.  A library keeps its extern "C" functions, its argument
 // checks, the judgement of the reset state, its result struct and thin __global__ kernels under its own names, which stage the
@@ -44,7 +45,7 @@ namespace sd = lle_search_device;
 using sd::fail;
 
 constexpr int THREADS = 256;  // lanes of a workgroup of every kernel that runs these bodies
-enum { CNT_STATES = 0, CNT_EXPANDED, CNT_GOAL, CNT_OVERFLOW, CNT_STEP_ERRORS, CNT_DENSE /* the trail kind's alone */, CNT_COUNT = 8 };
+enum { CNT_STATES = 0, CNT_EXPANDED, CNT_GOAL, CNT_OVERFLOW, CNT_STEP_ERRORS, CNT_DENSE /* the kinds with a walk: trail, cycle */, CNT_COUNT = 8 };
 constexpr unsigned long long NO_GOAL = ~0ull;
 
 struct Params {  // what every library's kernel parameters begin with
@@ -227,7 +228,7 @@ struct Outcome {
     int length = -1, depth_reached = 0;
     int64_t n_states = 1, step_errors = 0;
     unsigned long long dense = 0;        // work items whose walk ran out of budget, when the run ends with dense_status
-    uint32_t goal_extra[2] = {0u, 0u};   // the extra words of the plan's last state
+    uint32_t goal_extra[sl::MAX_EXTRA] = {};  // the extra words of the plan's last state
 };
 
 // The kernels of one piece: insert is the instantiation this run launches, with `lds` bytes of dynamic LDS; `staged`: it is <true>.

@@ -262,20 +262,30 @@ LLE_SEARCH_HD bool occupant_is(const Occupants& o, const RecordLayout& r, uint32
     return same_record(PoolRecord{o.pool, o.stride, occupant}, me, r.n_key);
 }
 
-// ---- records with extra words.  A KIND of search carries EXTRA (<= 2) more words of identity per record: the VALUE of the trajectory
+// ---- records with extra words.  A KIND of search carries EXTRA (<= MAX_EXTRA) more words of identity per record: the VALUE of the trajectory
 // that reached the state, hashed and compared after the key words.  The words live only in the pool, as the arrays n_words ..
 // n_words + EXTRA - 1 behind the record's: the batch has no buffer for them.  A kind says (PlainKind below; HelpKind of
-// ../helpgraph/helpgraph_logic.hpp; TrailKind of ../trails/trails_logic.hpp):
+// ../helpgraph/helpgraph_logic.hpp; TrailKind of ../trails/trails_logic.hpp; CycleKind of ../cycles/cycles_logic.hpp):
 //   EXTRA, Value      the word count, and the value as the kernels keep it per candidate between insert and commit
 //   state             the arcs of one state (`rec` its record, `cell` the map's cell table): all of it the value depends on
 //   successor         the value of a successor with those arcs whose parent is record `parent` of the pool; false: no value, the
 //                     run has no answer (the trail kind's walk ran out of budget)
 //   violates, accepts does the mode drop a trajectory with this value; may a goal state with it end a plan
 //   words             the value as ExtraWords
+constexpr int MAX_EXTRA = 21;  // the cycle kind's larger agent class (../cycles/cycles_logic.hpp)
 template <int EXTRA>
 struct ExtraWords {
-    static_assert(EXTRA >= 0 && EXTRA <= 2, "KeyWithExtra selects among at most two words");
+    static_assert(EXTRA >= 0 && EXTRA <= MAX_EXTRA, "a kind carries at most MAX_EXTRA words");
     uint32_t w[EXTRA > 0 ? EXTRA : 1];
+    // Word i, i < EXTRA not known at compile time: selects over the words, which so stay in registers.
+    LLE_SEARCH_HD uint32_t pick(int i) const {
+        uint32_t v = w[0];
+#if defined(__clang__)
+#pragma unroll
+#endif
+        for (int k = 1; k < EXTRA; k++) v = i == k ? w[k] : v;
+        return v;
+    }
 };
 // The IDENTITY of a record: the n_key key words of `rec`, then the extra words.  What hash_record and same_record read, with n_key + EXTRA words.
 template <class Record, int EXTRA>
@@ -283,7 +293,10 @@ struct KeyWithExtra {
     const Record& rec;
     int n_key;
     ExtraWords<EXTRA> x;
-    LLE_SEARCH_HD uint32_t operator()(int w) const { return w < n_key ? rec(w) : EXTRA > 1 && w > n_key ? x.w[EXTRA > 1] : x.w[0]; }
+    LLE_SEARCH_HD uint32_t operator()(int w) const {
+        if constexpr (EXTRA <= 2) return w < n_key ? rec(w) : EXTRA > 1 && w > n_key ? x.w[EXTRA > 1] : x.w[0];
+        else return w < n_key ? rec(w) : x.pick(w - n_key);
+    }
 };
 template <int EXTRA, class Record>
 LLE_SEARCH_HD KeyWithExtra<Record, EXTRA> key_with_extra(const Record& rec, int n_key, const ExtraWords<EXTRA>& x) { return {rec, n_key, x}; }

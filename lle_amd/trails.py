@@ -11,7 +11,7 @@ the longest trail that ends at agent a, and a trajectory is dropped the moment s
     TrailCharacterizer(world, 10).is_sequential(3)                   # does every plan within 10 steps hold such a trail
 
 Modes: "no-sequence[-N]" for 2 <= N <= 16, and everything `HelpGraphSolver` serves; "no-interdependence-N" for N >= 3 (a closed trail
-over exactly N distinct agents) is the one solve mode of the reference that is not built and raises NotImplementedError.
+over exactly N distinct agents) raises NotImplementedError here: `lle_amd.CycleSolver` (lle_amd.cycles) serves it.
 
 The module is loaded only when such a solver is asked for.  No fallback: a missing library raises.
 """
