@@ -68,8 +68,14 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // per-env-sources section of level 6 (12 + 5 rows) took a second pass for ONE row -- 2.3 us on every step with per-environment
 // sources (in-kernel stamps: tables in LDS 3.95 us after entry against 1.61; profiles/r04_pes_tax.md) --, config 5 (33 rows) three.
 // (named scalars, not an array: an indexed private array here ended up in scratch memory)
+// UNI: `wave_in_wg` is a scalar (the step kernels with row heads, through readfirstlane): every row guard below is then a scalar branch over an
+// unpredicated load / LDS write -- no exec masks, no zeroed registers.  The row index of a pass goes through an empty asm there, so that the
+// addresses of its eight rows are built from it where they are used: left to itself the compiler carries them round the loop (which runs
+// once on most maps) as eight scalar induction variables and their strides, in a kernel that has no scalar register to spare.
 #define LLE_COPY_ROWS(SRC)                                                                                              \
-    for (uint32_t r0 = wave_in_wg; r0 < rows; r0 += 8 * waves_per_wg) {                                                \
+    for (uint32_t rr = wave_in_wg; rr < rows; rr += 8 * waves_per_wg) {                                                \
+        uint32_t r0 = rr;                                                                                               \
+        if constexpr (UNI) asm volatile("" : "+s"(r0));                                                                 \
         const uint32_t r1 = r0 + waves_per_wg, r2 = r1 + waves_per_wg, r3 = r2 + waves_per_wg, r4 = r3 + waves_per_wg, \
                        r5 = r4 + waves_per_wg, r6 = r5 + waves_per_wg, r7 = r6 + waves_per_wg;                          \
         const u32x4 z = {0, 0, 0, 0};                                                                                   \
@@ -95,6 +101,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
             if (r7 < rows) dst[r7 * 64] = v7;                                                                           \
         }                                                                                                               \
     }
+template <bool UNI = false>
 __device__ __forceinline__ void copy_tables_to_lds(const uint8_t* __restrict__ tables, uint8_t* lds, uint32_t tab_bytes,
                                                    uint32_t lane, uint32_t wave_in_wg, uint32_t waves_per_wg) {
     const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(tables) + lane;
@@ -108,6 +115,7 @@ __device__ __forceinline__ void copy_tables_to_lds(const uint8_t* __restrict__ t
 // Two sections into consecutive LDS ranges (the map tables and, behind them, the per-env-sources section), with the rows of BOTH
 // requested before the first LDS write: called one after the other, the second copy's loads would only be issued once the
 // first copy's have returned.
+template <bool UNI = false>
 __device__ __forceinline__ void copy_tables2_to_lds(const uint8_t* __restrict__ t1, uint32_t bytes1, const uint8_t* __restrict__ t2, uint32_t bytes2,
                                                     uint8_t* lds, uint32_t lane, uint32_t wave_in_wg, uint32_t waves_per_wg) {
     const u32x4* __restrict__ s1 = reinterpret_cast<const u32x4*>(t1) + lane;
@@ -204,6 +212,13 @@ __device__ __forceinline__ void stream_store(uint4* p, const uint4& v) {
     }
 }
 
+// The same with the policy as a wave-uniform RUN-TIME flag: the cold paths of the kernels with row heads (HeadPath below) keep one copy of
+// their loops for both policies -- a scalar branch per store, out of line, instead of every loop compiled twice next to the hot one.
+__device__ __forceinline__ void stream_store_rt(uint4* p, const uint4& v, uint32_t wt) {
+    if (wt) stream_store<true>(p, v);
+    else stream_store<false>(p, v);
+}
+
 // Chunks [first + lane, n_chunks) of a row from LDS, 1 KiB per wave instruction; four LDS reads are in flight before the
 // first store so that a long row is not one LDS round trip per KiB.
 template <bool WT>
@@ -231,7 +246,7 @@ __device__ __forceinline__ void stream_whole_row(uint4* __restrict__ dst, const 
 }
 
 // The same without the row's HEAD (chunks [head_lo, head_lo + head_n) and, behind them, [head2_lo, head2_lo + head2_n): stored before
-// the state machine, see store_heads): tail chunk i is chunk i + (i >= head_lo ? head_n : 0), + head2_n once that reaches head2_lo.
+// the state machine, see store_heads_hot): tail chunk i is chunk i + (i >= head_lo ? head_n : 0), + head2_n once that reaches head2_lo.
 template <bool WT>
 __device__ __forceinline__ void stream_row_tail(uint4* __restrict__ dst, const uint4* srcv, uint32_t n_chunks, uint32_t head_lo, uint32_t head_n,
                                                 uint32_t lane, uint32_t head2_lo = 0, uint32_t head2_n = 0) {
@@ -249,6 +264,18 @@ __device__ __forceinline__ void stream_row_tail(uint4* __restrict__ dst, const u
     for (uint32_t i = lane + 128u; i < n_tail; i += 64u) {
         const uint32_t c = chunk_of(i);
         stream_store<WT>(dst + c, srcv[c]);
+    }
+}
+
+// ... and with the run-time policy (cold paths: one plain loop, no reads ahead)
+__device__ __forceinline__ void stream_row_tail_rt(uint4* __restrict__ dst, const uint4* srcv, uint32_t n_chunks, uint32_t head_lo, uint32_t head_n,
+                                                   uint32_t lane, uint32_t wt, uint32_t head2_lo = 0, uint32_t head2_n = 0) {
+    const uint32_t n_tail = n_chunks - head_n - head2_n;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = lane; i < n_tail; i += 64u) {
+        uint32_t c = i + (i >= head_lo ? head_n : 0u);
+        if (head2_n) c += c >= head2_lo ? head2_n : 0u;
+        stream_store_rt(dst + c, srcv[c], wt);
     }
 }
 
@@ -337,18 +364,38 @@ __device__ __forceinline__ void stream_wide_dyn(uint4* __restrict__ dst, const i
     }
 }
 
+// The kernels with row heads (step_kernel MODE 6 / 7 / 8) compile their head stores and their row loop twice -- not once per store policy:
+//   HP_HOT   what a launch with the default rules executes: write-through, every wavefront stores its own heads, no row rotation.  Straight-line:
+//            the trip count is a SCALAR (a wavefront's rows are wave-uniform: `n_rows` through readfirstlane), so the loops run on s_cmp /
+//            s_cbranch_scc with the row base advanced by the pitch, and nothing of the other rules is branched around.
+//   HP_COLD  every other rule (LLE_WRITE_THROUGH=0, LLE_HEAD_GROUP=2|4, LLE_ROW_ROTATE=1 and the launches that rotate by default, past the
+//            Infinity Cache): one copy with the policy as a run-time flag (stream_store_rt), placed behind the hot code.
+//   HP_NONE  the kernels without heads: as before (policy and width as template arguments, dispatch_stream).
+enum HeadPath { HP_NONE = 0, HP_HOT = 1, HP_COLD = 2 };
+
 // The heads of the wave's rows: the same `head_n` (<= 64) chunks, straight from the map's pristine template in global
 // memory (`v`: this lane's chunk), into every row.  Issued BEFORE the state machine: a launch of the step kernel is
 // (ramp) + (state machine, every wavefront at the same time) + (stream), and the lines that no agent, beam or gem can
 // touch need not wait for the state machine -- the memory system starts ~2 us earlier (tools/ceiling/head_probe.hip).
-template <bool WT>
-__device__ __forceinline__ void store_heads(int8_t* __restrict__ obs, uint64_t obs_stride, int64_t env0, int64_t n_here, uint32_t head_lo,
-                                            uint32_t head_n, const uint4& v, uint32_t lane, uint32_t rot = 0, uint32_t head2_lo = 0, uint32_t head2_n = 0) {
-    // (two runs: lanes [0, head_n) hold the chunks of the first, lanes [head_n, head_n + head2_n) those of the second)
+// (two runs: lanes [0, head_n) hold the chunks of the first, lanes [head_n, head_n + head2_n) those of the second)
+__device__ __forceinline__ void store_heads_hot(int8_t* __restrict__ obs, uint32_t obs_stride, int64_t env0, uint32_t n_rows, uint32_t head_lo, uint32_t head_n,
+                                                const uint4& v, uint32_t lane, uint32_t head2_lo, uint32_t head2_n) {
     const uint32_t chunk = lane < head_n ? head_lo + lane : head2_lo + (lane - head_n);
-    if (lane < head_n + head2_n)
-        for (uint32_t k = 0; k < (uint32_t)n_here; k++)
-            stream_store<WT>(reinterpret_cast<uint4*>(obs + (uint64_t)(env0 + rotated(k, rot, (uint32_t)n_here)) * obs_stride) + chunk, v);
+    if (lane < head_n + head2_n) {
+        uint8_t* p = reinterpret_cast<uint8_t*>(obs) + (uint64_t)env0 * obs_stride + (uint64_t)chunk * 16u;
+#pragma clang loop unroll(disable)
+        for (uint32_t k = 0; k < n_rows; k++, p += obs_stride) stream_store<true>(reinterpret_cast<uint4*>(p), v);
+    }
+}
+// ... under any other rule: the rows in the order of `rot` (row_rotation), the store policy in `wt`
+__device__ __forceinline__ void store_heads_cold(int8_t* __restrict__ obs, uint64_t obs_stride, int64_t env0, uint32_t n_rows, uint32_t head_lo, uint32_t head_n,
+                                                 const uint4& v, uint32_t lane, uint32_t rot, uint32_t head2_lo, uint32_t head2_n, uint32_t wt) {
+    const uint32_t chunk = lane < head_n ? head_lo + lane : head2_lo + (lane - head_n);
+    if (lane < head_n + head2_n) {
+#pragma clang loop unroll(disable)
+        for (uint32_t k = 0; k < n_rows; k++)
+            stream_store_rt(reinterpret_cast<uint4*>(obs + (uint64_t)(env0 + rotated(k, rot, n_rows)) * obs_stride) + chunk, v, wt);
+    }
 }
 
 // Store policy x element width of a launch as compile-time tags: f(std::bool_constant<WT>, std::bool_constant<WIDE>) is called for the one
@@ -370,19 +417,24 @@ __device__ __forceinline__ void dispatch_stream(uint32_t lflags, F&& f) {
 // ---- phase 2: layered observation of the wave's environments, one environment at a time.
 // `scratch` holds one hand-over record per environment: [0 | beam masks | ~gem bits | byte index of each agent].
 // `obs_stride` = bytes between the rows of consecutive environments in `obs`.
-// HEAD: the rows' heads are already stored (store_heads); stream the rest.
+// HEAD: the rows' heads are already stored (store_heads_hot); stream the rest.
 // INCR: only the dynamic chunks (dyn_chunks / n_dyn_chunks: stream_row_dyn).
 // WIDE: the row leaves as fp16 / bf16 / fp32 (tables.h ObsElem, `et`), stream_wide.  A template parameter, chosen by the caller OUTSIDE the loop
 // over the environments: with the choice inside it, the loop-invariant addresses of both streams were hoisted above the loop together and
 // 105 kernels at their register caps went to scratch.
-template <bool WT, bool HEAD = false, bool INCR = false, bool WIDE = false>
+// HP (HeadPath above; the kernels with row heads only): HP_HOT -- write-through, no rotation, scalar trip count; HP_COLD -- the policy in `wt_rt`.
+template <bool WT, bool HEAD = false, bool INCR = false, bool WIDE = false, int HP = HP_NONE>
 __device__ __forceinline__ void write_observations(int A, int L, uint32_t D, uint32_t n_chunks, uint64_t obs_stride,
                                                    const uint64_t* dyn, int8_t* tmpl, const uint32_t* scratch,
                                                    uint32_t scr_stride, int8_t* __restrict__ obs, int64_t env0,
                                                    int64_t n_here, uint32_t lane, uint32_t head_lo = 0, uint32_t head_n = 0, uint32_t rot = 0,
-                                                   const uint16_t* dyn_chunks = nullptr, uint32_t n_dyn_chunks = 0, uint32_t et = OBS_I8) {
+                                                   const uint16_t* dyn_chunks = nullptr, uint32_t n_dyn_chunks = 0, uint32_t et = OBS_I8, uint32_t wt_rt = 0) {
     // (`obs_stride` is the row pitch in BYTES: the map's pitch in elements times the element size)
     static_assert(!(WIDE && HEAD), "the kernels with row heads carry no widening code: the launcher never sends them a widened launch");
+    static_assert(HP == HP_NONE || (HEAD && !INCR && !WIDE && (HP == HP_COLD || WT)), "the hot path is the write-through tail stream");
+    // (HP: the rows of a wavefront are wave-uniform there -- said to the compiler, which then keeps the loop counter and the row base scalar)
+    const uint32_t n_rows = HP != HP_NONE ? (uint32_t)__builtin_amdgcn_readfirstlane((int)n_here) : (uint32_t)n_here;
+    if (HP == HP_HOT) rot = 0u;
     uint32_t dc0 = 0xFFFFu, dc1 = 0xFFFFu;
     if constexpr (INCR) {
         dc0 = lane < n_dyn_chunks ? (uint32_t)dyn_chunks[lane] : 0xFFFFu;
@@ -403,8 +455,8 @@ __device__ __forceinline__ void write_observations(int A, int L, uint32_t D, uin
     const bool is_agent_lane = (int)lane < A;
     const uint4* srcv = reinterpret_cast<const uint4*>(tmpl);
 
-    for (uint32_t k0 = 0; k0 < (uint32_t)n_here; k0++) {
-        const uint32_t k = rotated(k0, rot, (uint32_t)n_here);  // (row_rotation: the wavefront starts at another one of its rows)
+    for (uint32_t k0 = 0; k0 < n_rows; k0++) {
+        const uint32_t k = HP == HP_HOT ? k0 : rotated(k0, rot, n_rows);  // (row_rotation: the wavefront starts at another one of its rows)
         const uint32_t* sc = scratch + k * scr_stride;
         // (a) bytes that depend on beams / gems
         {
@@ -431,6 +483,7 @@ __device__ __forceinline__ void write_observations(int A, int L, uint32_t D, uin
             if constexpr (INCR) stream_wide_dyn<WT>(dst, tmpl, dyn_chunks, 0u, n_dyn_chunks, 0u, et, lane);
             else stream_wide<WT>(dst, tmpl, n_chunks, et, lane);
         } else if constexpr (INCR) stream_row_dyn<WT>(dst, srcv, dyn_chunks, n_dyn_chunks, dc0, dc1, lane);
+        else if constexpr (HP == HP_COLD) stream_row_tail_rt(dst, srcv, n_chunks, head_lo, head_n, lane, wt_rt);
         else if constexpr (HEAD) stream_row_tail<WT>(dst, srcv, n_chunks, head_lo, head_n, lane);
         else stream_whole_row<WT>(dst, srcv, n_chunks, lane);
         wave_sync();
@@ -541,7 +594,7 @@ __device__ __forceinline__ void elem_eval(uint32_t e, const uint32_t* sc, int A,
     val = type == ELEM_SOURCE ? -1 : 1;
     on = type == ELEM_SOURCE ? true : (is_gem ? ((sc[L + 1] >> i5) & 1u) != 0 : ((sc[1 + i5] >> off) & 1u) != 0);
 }
-template <bool WT, bool HEAD = false, bool INCR = false, bool WIDE = false>
+template <bool WT, bool HEAD = false, bool INCR = false, bool WIDE = false, int HP = HP_NONE>
 __device__ __forceinline__ void write_observations_env(int A, int L, uint32_t HW, uint32_t n_elems, uint32_t n_chunks,
                                                        uint64_t obs_stride, const uint32_t* elems, const int8_t* bare,
                                                        int8_t* tmpl, const uint32_t* scratch, uint32_t scr_stride,
@@ -549,8 +602,11 @@ __device__ __forceinline__ void write_observations_env(int A, int L, uint32_t HW
                                                        const uint8_t* laser_layer = nullptr, uint32_t gem_layer_in = 0xFFFFFFFFu,
                                                        uint32_t head_lo = 0, uint32_t head_n = 0, uint32_t rot = 0,
                                                        const uint16_t* dyn_chunks = nullptr, uint32_t n_dyn_chunks = 0, uint32_t head2_lo = 0, uint32_t head2_n = 0,
-                                                       uint32_t et = OBS_I8) {
+                                                       uint32_t et = OBS_I8, uint32_t wt_rt = 0) {
     static_assert(!(WIDE && HEAD), "no widening in the kernels with row heads");
+    static_assert(HP == HP_NONE || (HEAD && !INCR && !WIDE && (HP == HP_COLD || WT)), "the hot path is the write-through tail stream");
+    const uint32_t n_rows = HP != HP_NONE ? (uint32_t)__builtin_amdgcn_readfirstlane((int)n_here) : (uint32_t)n_here;  // (see write_observations)
+    if (HP == HP_HOT) rot = 0u;
     uint32_t dc0 = 0xFFFFu, dc1 = 0xFFFFu;  // INCR: this lane's first two dynamic chunks (stream_row_dyn)
     if constexpr (INCR) {
         dc0 = lane < n_dyn_chunks ? (uint32_t)dyn_chunks[lane] : 0xFFFFu;
@@ -572,8 +628,8 @@ __device__ __forceinline__ void write_observations_env(int A, int L, uint32_t HW
     const uint32_t e0_always = (has_e0 && e0_src) ? 1u : 0u, e0_dyn = (has_e0 && !e0_src) ? 1u : 0u;
     const bool is_agent_lane = (int)lane < A;
     const uint4* srcv = reinterpret_cast<const uint4*>(tmpl);
-    for (uint32_t k0 = 0; k0 < (uint32_t)n_here; k0++) {
-        const uint32_t k = rotated(k0, rot, (uint32_t)n_here);
+    for (uint32_t k0 = 0; k0 < n_rows; k0++) {
+        const uint32_t k = HP == HP_HOT ? k0 : rotated(k0, rot, n_rows);
         const uint32_t* sc = scratch + k * scr_stride;
         const uint32_t colour = (sc[e0_colw] >> e0_colsh) & 0xFFu, onw = sc[e0_onw];
         uint32_t idx0 = e0_base + __umul24(colour, e0_mul);
@@ -593,7 +649,8 @@ __device__ __forceinline__ void write_observations_env(int A, int L, uint32_t HW
             if constexpr (INCR) stream_wide_dyn<WT>(dst, tmpl, dyn_chunks, 0u, n_dyn_chunks, 0u, et, lane);
             else stream_wide<WT>(dst, tmpl, n_chunks, et, lane);
         } else if constexpr (INCR) stream_row_dyn<WT>(dst, srcv, dyn_chunks, n_dyn_chunks, dc0, dc1, lane);
-        else if constexpr (HEAD) stream_row_tail<WT>(dst, srcv, n_chunks, head_lo, head_n, lane, head2_lo, head2_n);  // (the head is stored already: store_heads)
+        else if constexpr (HP == HP_COLD) stream_row_tail_rt(dst, srcv, n_chunks, head_lo, head_n, lane, wt_rt, head2_lo, head2_n);
+        else if constexpr (HEAD) stream_row_tail<WT>(dst, srcv, n_chunks, head_lo, head_n, lane, head2_lo, head2_n);  // (the head is stored already: store_heads_hot)
         else stream_whole_row<WT>(dst, srcv, n_chunks, lane);
         wave_sync();
         // bare bytes back (LDS is in order: after the reads above, before the next environment's writes).  On the agent / laser

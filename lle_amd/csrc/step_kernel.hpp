@@ -65,6 +65,16 @@ __device__ __forceinline__ const EnvOutputs* kernarg_env_out() {
     return reinterpret_cast<const EnvOutputs*>((const char*)__builtin_amdgcn_kernarg_segment_ptr() + KERNARG_ENV_OUT);  // (C cast: out of the constant address space)
 }
 
+// A wave-uniform value parked in a VECTOR register and fetched back: the kernels with row heads hold their wavefront's id and first environment
+// in scalar registers (see wave_in_wg below), which the state machine is short of and the late code needs again; vector registers it has.
+// Both ends sit in wave-uniform control flow with every lane active.
+__device__ __forceinline__ uint32_t park_uniform(uint32_t s) {
+    uint32_t v;
+    asm("v_mov_b32 %0, %1" : "=v"(v) : "s"(s));
+    return v;
+}
+__device__ __forceinline__ uint32_t unpark_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
 template <int G, int LM, int MODE, bool ML1, int LX = -1>
 __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P, LaunchArgs K) {
     // MODE 9: MODE 4 whose launch writes the PARTIAL k x k observation (python/lle/observations.py:312-369) from the hand-over records
@@ -105,7 +115,12 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
     const uint32_t EPW = K.envs_per_wave < (uint32_t)(64 / G) ? K.envs_per_wave : (uint32_t)(64 / G);
     constexpr int NW = (2 * G + 7) / 8;             // 64-bit words of the event list (2 events per agent at most)
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const uint32_t lane = threadIdx.x & 63u, wave_in_wg = threadIdx.x >> 6, waves_per_wg = blockDim.x >> 6;
+    const uint32_t lane = threadIdx.x & 63u, waves_per_wg = blockDim.x >> 6;
+    // HEAD: the wavefront's index as a SCALAR (the compiler does not know that threadIdx.x >> 6 is wave-uniform): the wavefront's id, its first
+    // environment and its number of rows then live in scalar registers, the loops over its rows run on s_cmp / s_cbranch_scc instead of exec
+    // masks, and the row guards of the table copy become scalar branches.  The kernels with row heads only: the rollout instantiations sit at
+    // their register caps and stay as they are.
+    const uint32_t wave_in_wg = HEAD ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : threadIdx.x >> 6;
     const uint32_t blk = xcd_block_dir(blockIdx.x, gridDim.x, K.flags);  // the block of environments this workgroup serves
     const uint32_t wave_id = blk * waves_per_wg + wave_in_wg;
     const uint8_t* __restrict__ tables = P.tables;
@@ -163,7 +178,14 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
     uint32_t h_init_beams[LR];  // the reset state's beams (shared record; the per-env one is read where it is used)
 #pragma unroll
     for (int b = 0; b < LR; b++) h_init_beams[b] = (!BM && b < L) ? initp->beams[b] : 0u;
-    const int64_t n_here = (K.env_limit - env0) < (int64_t)EPW ? (K.env_limit - env0) : (int64_t)EPW;
+    const int64_t n_left = K.env_limit - env0;
+    // (HEAD: clamped at zero -- every use asks `n_here > 0` first -- so that the count is ONE scalar register, not a pair)
+    const int64_t n_here = HEAD ? (int64_t)(n_left < 0 ? 0u : (n_left < (int64_t)EPW ? (uint32_t)n_left : EPW)) : (n_left < (int64_t)EPW ? n_left : (int64_t)EPW);
+    const uint32_t n_rows = n_here > 0 ? (uint32_t)n_here : 0u;  // (HEAD: a scalar, see wave_in_wg)
+    // HEAD: the rules of this launch are the default ones -- write-through, every wavefront stores its own heads, no row rotation -- and the
+    // straight-line copies of the head stores and of the row loop serve it (obs_stream.hpp HeadPath); anything else takes the cold copies.
+    constexpr uint32_t HOT_RULES = LAUNCH_WRITE_THROUGH | LAUNCH_ROTATE_ROWS | (MODE == 6 ? LAUNCH_HEAD_GROUP2 | LAUNCH_HEAD_GROUP4 : 0u);
+    const bool hot = HEAD && (K.flags & HOT_RULES) == LAUNCH_WRITE_THROUGH;
     const uint32_t amask = (1u << A) - 1u;
     // (the row this wavefront starts its stream at, obs_stream.hpp row_rotation: computed where it is used, from values that are live
     // there anyway -- carried across the state machine it cost the tightest instantiations a spilled register)
@@ -282,12 +304,32 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
     // kernel is therefore issued first -- the head chunk, the state, the caller's actions, the table rows -- and has
     // returned before the first store: the vmcnt counter is in order, so a load waited for AFTER the head stores would
     // wait for their acknowledgements (and the compiler does not see the `sc1` stores, which are inline asm).
-    const uint32_t head_lo = HEAD ? (PES ? hdr->pes_head_lo : hdr->head_lo) : 0u;
-    const uint32_t head_n = (HEAD && write_obs && !split && !incr) ? (PES ? hdr->pes_head_n : hdr->head_n) : 0u;  // (incr: static lines are not written at all)
+    uint32_t head_lo = HEAD ? (PES ? hdr->pes_head_lo : hdr->head_lo) : 0u;
+    // (read unconditionally, chosen afterwards: a read under `write_obs` is a scalar load that waits for the one of `obs_supported` -- a
+    // dependent round trip in front of every other load of the prologue)
+    const uint32_t head_n_map = HEAD ? (PES ? hdr->pes_head_n : hdr->head_n) : 0u, head2_n_map = (HEAD && PES) ? hdr->pes_head2_n : 0u;
+    const uint32_t head_n = (HEAD && write_obs && !split && !incr) ? head_n_map : 0u;  // (incr: static lines are not written at all)
     // (per-environment sources: a second run of colour-independent lines behind the first, tables.h pes_head2_*)
-    const uint32_t head2_lo = (HEAD && PES) ? hdr->pes_head2_lo : 0u, head2_n = (HEAD && PES && head_n) ? hdr->pes_head2_n : 0u;
+    const uint32_t head2_lo = (HEAD && PES) ? hdr->pes_head2_lo : 0u, head2_n = (HEAD && PES && head_n) ? head2_n_map : 0u;
     uint4 head_v = {0u, 0u, 0u, 0u};
     if (HEAD) {
+        // Every scalar the prologue reads from the map's header and its reset record, in ONE batch behind the kernel arguments: the empty asm
+        // statements want them all in registers where `head_lo` -- the address of the first vector load -- is made, so the loads are issued
+        // together and waited for once.  Left to the compiler they came in three batches, each behind the previous one's wait -- the last of
+        // them, with the offsets the table rows need, behind the state loads.  (The later reads of the same fields are the same values to the
+        // compiler: nothing is read twice.  Not `volatile`, no memory clobber: behind either the compiler reads the header with vector loads.)
+        const uint32_t q_lay = hdr->off_cell_lay, q_lds = hdr->lds_table_bytes, q_ig = initp->gems;
+        const uint64_t q_ib = initp->bits;
+        asm("" : "+s"(head_lo) : "s"(h_HW), "s"(h_obs_stride), "s"(h_n_chunks), "s"(h_D), "s"(h_enabled), "s"(h_off_cell_meta), "s"(h_off_dyn), "s"(h_off_template),
+                                 "s"(head_n_map), "s"(q_lay), "s"(q_lds), "s"(q_ig), "s"((uint32_t)q_ib), "s"((uint32_t)(q_ib >> 32)), "s"(A), "s"(W),
+                                 "s"((uint32_t)hdr->obs_supported));
+#pragma unroll
+        for (int b = 0; b < LR; b++)
+            if (!BM && b < L) asm("" : "+s"(head_lo) : "s"(h_beam_full[b]), "s"(h_init_beams[b]));
+        if (BM) asm("" : "+s"(head_lo) : "s"(h_chain));
+        if (PES) asm("" : "+s"(head_lo) : "s"(h_off_recolour), "s"(h_off_bare), "s"(h_off_elems), "s"(h_n_elems), "s"(head2_lo), "s"(head2_n_map), "s"((uint32_t)hdr->ext_bytes),
+                                          "s"((uint32_t)hdr->recolour_exact));
+        if (ENV_OUT) asm("" : "+s"(head_lo) : "s"(h_G), "s"(h_H));
         if (lane < head_n + head2_n)
             head_v = reinterpret_cast<const uint4*>(tables + (PES ? h_off_bare : h_off_template))[lane < head_n ? head_lo + lane : head2_lo + (lane - head_n)];
         LLE_LOAD_STATE();
@@ -328,12 +370,12 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
         if (lane < TMPL_NEG_MAX) pre_neg = reinterpret_cast<const uint32_t*>(tables + sizeof(MapHeader) + tmpl_bits_bytes(h_n_chunks))[lane];
         if (!HEAD) LLE_LOAD_STATE();
     }
-    if (PES) copy_tables2_to_lds(tables + tab_off, tab_bytes, tables + h_off_bare, ext_bytes, lds, lane, wave_in_wg, waves_per_wg);
+    if (PES) copy_tables2_to_lds<HEAD>(tables + tab_off, tab_bytes, tables + h_off_bare, ext_bytes, lds, lane, wave_in_wg, waves_per_wg);
     else if (use_sets) copy_tables2_to_lds(tables + tab_off, tab_bytes, K.win_sets + (uint64_t)map_idx * win_table_bytes(hdr->HW), ext_bytes, lds, lane, wave_in_wg, waves_per_wg);
     else if (CAN_SPLIT && GEN && split && (K.flags & LAUNCH_PACKED_TABLES))  // (many maps, few environments each: obs_stream.hpp expand_packed_tables)
         expand_packed_tables(tables + hdr->off_packed, lds, h_HW, hdr->packed_n_lay, h_off_cell_meta - tab_off, h_off_dyn - tab_off, h_off_template - h_off_dyn,
                              threadIdx.x, blockDim.x);
-    else copy_tables_to_lds(tables + tab_off, lds, tab_bytes, lane, wave_in_wg, waves_per_wg);
+    else copy_tables_to_lds<HEAD>(tables + tab_off, lds, tab_bytes, lane, wave_in_wg, waves_per_wg);
     constexpr uint32_t bt_bytes = BM ? 2u * LM * 4u : 0u;
     uint32_t* beam_tab = reinterpret_cast<uint32_t*>(lds + tab_bytes + ext_bytes);
     if (BM && (int)threadIdx.x < L) {
@@ -355,12 +397,14 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
         // head stores and in the state machine -- where it would wait for the stores as well
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
         const uint32_t hgroup = MODE != 6 ? 1u : ((K.flags & LAUNCH_HEAD_GROUP4) ? 4u : ((K.flags & LAUNCH_HEAD_GROUP2) ? 2u : 1u));  // (the default kernel only)
-        if (hgroup == 1u) {
-            if (head_n && n_here > 0) {
-                if (K.flags & LAUNCH_WRITE_THROUGH) store_heads<true>(P.obs, h_obs_stride, env0, n_here, head_lo, head_n, head_v, lane, LLE_ROT(), head2_lo, head2_n);
-                else store_heads<false>(P.obs, h_obs_stride, env0, n_here, head_lo, head_n, head_v, lane, LLE_ROT(), head2_lo, head2_n);
-            }
+        const uint32_t wt = K.flags & LAUNCH_WRITE_THROUGH;
+        if (__builtin_expect(hot, 1)) {
+            // the path of a launch with the default rules (obs_stream.hpp HeadPath): falls through; everything else sits behind the kernel's hot code
+            if (head_n && n_rows) store_heads_hot(P.obs, h_obs_stride, env0, n_rows, head_lo, head_n, head_v, lane, head2_lo, head2_n);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // LDS only: not the head stores' acknowledgements
+        } else if (hgroup == 1u) {
+            if (head_n && n_rows) store_heads_cold(P.obs, h_obs_stride, env0, n_rows, head_lo, head_n, head_v, lane, LLE_ROT(), head2_lo, head2_n, wt);
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         } else {
             // Phase shift inside the workgroup (round 4): one wavefront of every `hgroup` stores the heads of the whole group's rows (they are
             // the same bytes for every row), the others go straight to their state machines -- their tails then stream while the head
@@ -371,10 +415,7 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
                     const int64_t e0q = env0 + (int64_t)q * EPW;
                     int64_t nq = K.env_limit - e0q;
                     nq = nq < 0 ? 0 : (nq > (int64_t)EPW ? (int64_t)EPW : nq);
-                    if (nq > 0) {
-                        if (K.flags & LAUNCH_WRITE_THROUGH) store_heads<true>(P.obs, h_obs_stride, e0q, nq, head_lo, head_n, head_v, lane);
-                        else store_heads<false>(P.obs, h_obs_stride, e0q, nq, head_lo, head_n, head_v, lane);
-                    }
+                    if (nq > 0) store_heads_cold(P.obs, h_obs_stride, e0q, (uint32_t)nq, head_lo, head_n, head_v, lane, 0u, 0u, 0u, wt);
                 }
             }
         }
@@ -383,6 +424,9 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
         if (!(CAN_SPLIT && split)) LLE_LOAD_STATE();  // (split rows: requested ahead of the table rows, above)
     }
 
+    // (HEAD: the wavefront's id and first environment leave the scalar registers here and come back behind the state machine)
+    const uint32_t pk_wave = HEAD ? park_uniform(wave_id) : 0u, pk_env_lo = HEAD ? park_uniform((uint32_t)env0) : 0u,
+                   pk_env_hi = HEAD ? park_uniform((uint32_t)((uint64_t)env0 >> 32)) : 0u;
     const uint64_t* cell_lay = reinterpret_cast<const uint64_t*>(lds);
     const uint32_t* cell_meta = reinterpret_cast<const uint32_t*>(lds + (h_off_cell_meta - tab_off));
     const uint64_t* dyn = reinterpret_cast<const uint64_t*>(lds + (h_off_dyn - tab_off));
@@ -583,6 +627,9 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
     // positions, beams and gems only, so a wavefront of the OLDER half of the grid (the one the SIMD serves first, i.e.
     // the one whose first store ends the idle time of the memory system) does this after its stream, a younger one --
     // which waits for memory anyway and would otherwise add it to the end of the launch -- before.
+    const uint32_t wave_id_l = HEAD ? unpark_uniform(pk_wave) : wave_id;
+    const int64_t env0_l = HEAD ? (int64_t)(((uint64_t)unpark_uniform(pk_env_hi) << 32) | unpark_uniform(pk_env_lo)) : env0;
+#define LLE_ROT_L() ((ROLL && PES) ? 0u : row_rotation(wave_id_l, EPW, n_here, K.flags))
     auto post_step = [&]() {
     LLE_ENV_LATE(env_p);
     if (stepped) avail_lanes<G>(a, me, pos, occ, alive, arrived, meta_step, avail);
@@ -674,7 +721,7 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
                 if (staged) {
                     wave_sync();  // (LDS operations of a wavefront execute in order)
                     const float4* src4 = reinterpret_cast<const float4*>(reinterpret_cast<uint8_t*>(scratch) + st_off);
-                    float4* dst4 = reinterpret_cast<float4*>(O.state + env0 * len);  // (len * 4 is a multiple of 16: so is env0 * len * 4)
+                    float4* dst4 = reinterpret_cast<float4*>(O.state + env0_l * len);  // (len * 4 is a multiple of 16: so is env0 * len * 4)
                     const uint32_t n4 = n_here > 0 ? (uint32_t)n_here * (uint32_t)len / 4u : 0u;
                     for (uint32_t c = lane; c < n4; c += 64u) dst4[c] = src4[c];
                     wave_sync();
@@ -765,22 +812,43 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
         const EnvOutputs O = load_uniform(kernarg_env_out());
         if (O.partial && n_here > 0)
             write_partial<true>(A, L, W, (int)K.partial_k, part_pitch, K.partial_E, h_max_layers, cell_lay, cell_meta, part_bm, part_col, tmpl, scratch,
-                                scr_stride, O.partial, env0, n_here, lane, use_sets ? reinterpret_cast<const uint64_t*>(lds + tab_bytes) : nullptr, et);
-    } else if (write_obs && n_here > 0) {
+                                scr_stride, O.partial, env0_l, n_here, lane, use_sets ? reinterpret_cast<const uint64_t*>(lds + tab_bytes) : nullptr, et);
+    } else if (HEAD && write_obs && n_here > 0) {
+        // (obs_stream.hpp HeadPath: the straight-line copy for a launch with the default rules, one cold copy for every other rule;
+        // the rules are read from the flags again -- behind an empty asm, or the compiler carries `hot` across the state machine in a register pair)
+        uint32_t lflags = K.flags;
+        asm volatile("" : "+s"(lflags));
+        if (__builtin_expect((lflags & HOT_RULES) == LAUNCH_WRITE_THROUGH, 1)) {
+            if (PES)
+                write_observations_env<true, true, false, false, HP_HOT>(A, L, h_HW, h_n_elems, h_n_chunks, LLE_PITCH(), elems, bare, tmpl, scratch, scr_stride, obs_out, env0_l, n_here,
+                                                                         lane, nullptr, 0xFFFFFFFFu, head_lo, head_n, 0u, nullptr, 0u, head2_lo, head2_n, et);
+            else
+                write_observations<true, true, false, false, HP_HOT>(A, L, h_D, h_n_chunks, LLE_PITCH(), dyn, tmpl, scratch, scr_stride, obs_out, env0_l, n_here, lane, head_lo, head_n,
+                                                                     0u, nullptr, 0u, et);
+        } else {
+            if (PES)
+                write_observations_env<false, true, false, false, HP_COLD>(A, L, h_HW, h_n_elems, h_n_chunks, LLE_PITCH(), elems, bare, tmpl, scratch, scr_stride, obs_out, env0_l, n_here,
+                                                                           lane, nullptr, 0xFFFFFFFFu, head_lo, head_n, LLE_ROT_L(), nullptr, 0u, head2_lo, head2_n, et,
+                                                                           K.flags & LAUNCH_WRITE_THROUGH);
+            else
+                write_observations<false, true, false, false, HP_COLD>(A, L, h_D, h_n_chunks, LLE_PITCH(), dyn, tmpl, scratch, scr_stride, obs_out, env0_l, n_here, lane, head_lo, head_n,
+                                                                       LLE_ROT_L(), nullptr, 0u, et, K.flags & LAUNCH_WRITE_THROUGH);
+        }
+    } else if (!HEAD && write_obs && n_here > 0) {
         dispatch_stream<!HEAD>(K.flags, [&](auto wt_, auto wide_) {  // see stream_store (obs_stream.hpp)
             constexpr bool WT = decltype(wt_)::value, WIDE = decltype(wide_)::value;
             if (PES && CAN_INCR && incr)
-                write_observations_env<WT, false, true, WIDE>(A, L, h_HW, h_n_elems, h_n_chunks, LLE_PITCH(), elems, bare, tmpl, scratch, scr_stride, obs_out, env0, n_here,
-                                                              lane, nullptr, 0xFFFFFFFFu, 0u, 0u, LLE_ROT(), dyn_chunks, h_n_dyn_chunks, 0u, 0u, et);
+                write_observations_env<WT, false, true, WIDE>(A, L, h_HW, h_n_elems, h_n_chunks, LLE_PITCH(), elems, bare, tmpl, scratch, scr_stride, obs_out, env0_l, n_here,
+                                                              lane, nullptr, 0xFFFFFFFFu, 0u, 0u, LLE_ROT_L(), dyn_chunks, h_n_dyn_chunks, 0u, 0u, et);
             else if (PES)
-                write_observations_env<WT, HEAD, false, WIDE>(A, L, h_HW, h_n_elems, h_n_chunks, LLE_PITCH(), elems, bare, tmpl, scratch, scr_stride, obs_out, env0, n_here,
-                                                              lane, nullptr, 0xFFFFFFFFu, head_lo, head_n, LLE_ROT(), nullptr, 0u, head2_lo, head2_n, et);
+                write_observations_env<WT, HEAD, false, WIDE>(A, L, h_HW, h_n_elems, h_n_chunks, LLE_PITCH(), elems, bare, tmpl, scratch, scr_stride, obs_out, env0_l, n_here,
+                                                              lane, nullptr, 0xFFFFFFFFu, head_lo, head_n, LLE_ROT_L(), nullptr, 0u, head2_lo, head2_n, et);
             else if (CAN_INCR && incr)
-                write_observations<WT, false, true, WIDE>(A, L, h_D, h_n_chunks, LLE_PITCH(), dyn, tmpl, scratch, scr_stride, obs_out, env0, n_here, lane, 0u, 0u, LLE_ROT(),
+                write_observations<WT, false, true, WIDE>(A, L, h_D, h_n_chunks, LLE_PITCH(), dyn, tmpl, scratch, scr_stride, obs_out, env0_l, n_here, lane, 0u, 0u, LLE_ROT_L(),
                                                           dyn_chunks, h_n_dyn_chunks, et);
             else
-                write_observations<WT, HEAD, false, WIDE>(A, L, h_D, h_n_chunks, LLE_PITCH(), dyn, tmpl, scratch, scr_stride, obs_out, env0, n_here, lane, head_lo, head_n,
-                                                          LLE_ROT(), nullptr, 0u, et);
+                write_observations<WT, HEAD, false, WIDE>(A, L, h_D, h_n_chunks, LLE_PITCH(), dyn, tmpl, scratch, scr_stride, obs_out, env0_l, n_here, lane, head_lo, head_n,
+                                                          LLE_ROT_L(), nullptr, 0u, et);
         });
     }
     wave_sync();
@@ -810,6 +878,7 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
 #undef LLE_ENV_LATE
 #undef LLE_LOAD_STATE
 #undef LLE_ROT
+#undef LLE_ROT_L
 #undef LLE_ET
 #undef LLE_PITCH
     }
@@ -817,7 +886,7 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
         cnt.steps = cnt_lds[0]; cnt.gems = cnt_lds[1]; cnt.exits = cnt_lds[2]; cnt.died = cnt_lds[3];
         cnt.invalid = cnt_lds[4]; cnt.resets = cnt_lds[5]; cnt.bonus = cnt_lds[6];
     }
-    flush_stats(P.stats, wave_id, cnt, A, lane, PRE_STATS, stats_old);
+    flush_stats(P.stats, HEAD ? unpark_uniform(pk_wave) : wave_id, cnt, A, lane, PRE_STATS, stats_old);
     if (STAMPED && stamps) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         LLE_STAMP(6);

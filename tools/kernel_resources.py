@@ -3,13 +3,15 @@
     python3 tools/kernel_resources.py [--out profiles/rNN_kernel_resources.md] [files ...]
 
 Compiles the translation units of lle_amd/csrc (default: all .hip files) for gfx950 without linking -- no GPU needed --
-and writes one row per kernel: VGPRs, SGPRs, scratch bytes per lane, spills, occupancy."""
+and writes one row per kernel: code bytes, VGPRs, SGPRs, scratch bytes per lane, spills, occupancy.  The code bytes are the
+`codeLenInByte` the compiler prints behind each kernel of the device assembly (-S of the device side only)."""
 import argparse
 import concurrent.futures
 import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lle_amd", "csrc")
@@ -22,9 +24,12 @@ def demangle(names):
 
 
 def analyse(path):
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage",
-           "-c", path, "-o", os.devnull]
-    err = subprocess.run(cmd, cwd=CSRC, stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True).stderr
+    with tempfile.TemporaryDirectory() as tmp:
+        asm = os.path.join(tmp, "device.s")
+        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage",
+               "--cuda-device-only", "-S", path, "-o", asm]
+        err = subprocess.run(cmd, cwd=CSRC, stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True).stderr
+        code = code_bytes(asm) if os.path.exists(asm) else {}
     rows, cur = [], None
     for line in err.splitlines():
         m = re.search(r"remark:\s+Function Name: (\S+)", line)
@@ -35,7 +40,25 @@ def analyse(path):
         m = re.search(r"remark:\s+([A-Za-z \[\]/]+): (\S+)", line)
         if m and cur is not None and m.group(1).strip() in FIELDS:
             cur[m.group(1).strip()] = m.group(2)
+    for r in rows:
+        r["code"] = code.get(r["name"])
     return os.path.basename(path), rows
+
+
+def code_bytes(asm_path):
+    """{mangled kernel name: codeLenInByte} of a device assembly file."""
+    out, cur = {}, None
+    with open(asm_path) as f:
+        for line in f:
+            m = re.match(r"^(\w+):\s", line)
+            if m and not line.startswith("."):
+                cur = m.group(1)
+                continue
+            m = re.match(r"^; codeLenInByte = (\d+)", line)
+            if m and cur is not None:
+                out[cur] = int(m.group(1))
+                cur = None
+    return out
 
 
 def main():
@@ -56,12 +79,12 @@ def main():
         if not rows:
             continue
         names = demangle([r["name"] for r in rows])
-        lines += [f"## {fname} ({len(rows)} kernels)", "", "| kernel | VGPRs | SGPRs | scratch B/lane | SGPR spill | VGPR spill | waves/SIMD |", "|---|---|---|---|---|---|---|"]
+        lines += [f"## {fname} ({len(rows)} kernels)", "", "| kernel | VGPRs | SGPRs | scratch B/lane | SGPR spill | VGPR spill | waves/SIMD | code bytes |", "|---|---|---|---|---|---|---|---|"]
         for r, nm in zip(rows, names):
             total += 1
             scratch = int(r.get("ScratchSize [bytes/lane]", 0))
             spilled += scratch > 0
-            lines.append(f"| `{nm}` | {r.get('VGPRs')} | {r.get('TotalSGPRs')} | {scratch} | {r.get('SGPRs Spill')} | {r.get('VGPRs Spill')} | {r.get('Occupancy [waves/SIMD]')} |")
+            lines.append(f"| `{nm}` | {r.get('VGPRs')} | {r.get('TotalSGPRs')} | {scratch} | {r.get('SGPRs Spill')} | {r.get('VGPRs Spill')} | {r.get('Occupancy [waves/SIMD]')} | {r.get('code')} |")
         lines.append("")
     lines.insert(2, f"{total} kernels, {spilled} with scratch.\n")
     text = "\n".join(lines) + "\n"

@@ -17,7 +17,7 @@
   placement   several arenas of the same batch side by side: does the write rate depend on where a buffer lands?
   heads       row heads (lle_map_set_head_lines): us per launch by head size, over maps and batch sizes
   stamps      in-kernel s_memrealtime timeline of the step kernel (--fine: per-quarter view of a stamped MODE-0 build)
-  target      a fixed workload for `rocprofv3 --pmc ... -- python3 tools/lle_prof.py target ...` (step / noobs / partial / cfg5 / hbm)
+  target      a fixed workload for `rocprofv3 --pmc ... -- python3 tools/lle_prof.py target ...` (step / fill / outputs / pes / noobs / partial / cfg5 / hbm)
 
 Every timing is launch-to-launch over HIP events on torch's current stream (the stream every launch uses)."""
 import argparse
@@ -460,6 +460,18 @@ def cmd_target(args):
         bw.set_sources(torch.randint(0, bw.map.n_agents, (n, bw.map.n_sources), generator=g, dtype=torch.uint8))
         for t in range(args.iters):
             bw.step(sample=True, auto_reset=True, seed=1, t=t, recolour_resets=True)
+    elif what == "outputs":  # the fused LLE.step outputs written by the step launch: step_kernel MODE 7 / 4
+        bw = BatchedWorld(the_map(args), n)
+        A, G = bw.map.n_agents, bw.map.n_gems
+        st, rw, av = (torch.empty((n, 3 * A + G), device="cuda"), torch.empty((n, 1), device="cuda"), torch.empty((n, A, 5), dtype=torch.uint8, device="cuda"))
+        eo = bw.make_env_outputs(state=st, reward=rw, available=av)
+        for t in range(args.iters):
+            bw.step(sample=True, auto_reset=True, seed=1, t=t, env_out=eo)
+    elif what == "fill":  # the row-fill probe of the step kernel's shape (lle_batch_probe_row_fill): the same stores, no state machine
+        bw = BatchedWorld(the_map(args), n)
+        probe = bw.row_fill_prober()
+        for _ in range(args.iters):
+            probe()
     else:  # step | noobs | cfg5 | hbm
         m = Map(mapgen.config5(0), row_align=args.row_align) if what == "cfg5" else the_map(args)
         bw = BatchedWorld(m, 262144 if what == "hbm" and n == 65536 else n, obs_dtype=getattr(args, "obs_dtype", None))
@@ -494,7 +506,7 @@ def main():
             p.add_argument("--outputs", default=None, help="comma list of fused LLE.step outputs (state,reward,done,available) or 'none': lle_batch_step_outputs, diagnostic build only")
             p.add_argument("--general", action="store_true", help="two copies of the map, half of the environments each: the general (several maps) build")
         if name == "target":
-            p.add_argument("what", choices=["step", "noobs", "partial", "perspective", "cfg5", "hbm", "pes"])
+            p.add_argument("what", choices=["step", "fill", "outputs", "noobs", "partial", "perspective", "cfg5", "hbm", "pes"])
             p.add_argument("-k", type=int, default=7, help="window of the partial observer")
             p.add_argument("--obs-dtype", default=None, help="element type of the rows (step / hbm / cfg5): int8 (default), float16, bfloat16, float32")
     args = ap.parse_args()
