@@ -48,6 +48,9 @@ def __getattr__(name):
     if name in ("HelpForestSolver", "HelpForestResult", "ManyHelpCharacterization"):  # (the help-graph and trail modes over many maps, liblle_helpforest.so)
         from . import helpforest
         return getattr(helpforest, name)
+    if name in ("CycleForestSolver", "CycleForestResult", "ManyCycleCharacterization"):  # (no-interdependence-N over many maps, liblle_cycleforest.so)
+        from . import cycleforest
+        return getattr(cycleforest, name)
     if name in ("Predicate", "Solvable", "Independent", "Cooperative", "Asymmetric", "Sequential", "Convergent", "Divergent", "Interdependent", "And", "Or",
                 "Not", "WorldRequirements", "Constraint", "WorldFilter", "generate_n"):  # (lle.generator: the filter vocabulary)
         from . import generator
@@ -68,4 +71,4 @@ __all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorl
            "ForestSolver", "ForestResult", "solve_many", "characterize_many", "Constraint", "WorldFilter", "generate_n",
            "OptimalPolicy", "PolicyCapacityError", "HelpGraphSolver", "HelpGraphCharacterizer", "TrailSolver", "TrailCharacterizer",
            "HelpForestSolver", "HelpForestResult", "ManyHelpCharacterization", "TemporalCooperationTracker",
-           "CycleSolver", "CycleCharacterizer"]
+           "CycleSolver", "CycleCharacterizer", "CycleForestSolver", "CycleForestResult", "ManyCycleCharacterization"]

@@ -235,6 +235,13 @@ class CycleSolver(solver.Solver):
                                closed_orders=None if stats["closed_orders"] is None else list(stats["closed_orders"]))
         return plan
 
+    def forget(self):
+        """Drop the cached plans of this solver and of the inner ones; the device handles stay (for whoever times a search)."""
+        solver_ = self
+        while solver_ is not None:
+            solver_._cache.clear()
+            solver_ = getattr(solver_, "_inner", None)
+
     def free(self):
         if getattr(self, "h", None):
             try:
@@ -275,6 +282,11 @@ class CycleCharacterizer(TrailCharacterizer):
         if not self._shortest_path_profile.is_interdependent(n_agents):
             return False
         return self.compute_shortest_non_interdependent_path(n_agents) is None
+
+    def forget(self):
+        """Drop every cached answer, here and in the solvers behind; the device handles stay."""
+        self._results.clear()
+        self._solver.forget()
 
     def __eq__(self, other):
         return isinstance(other, CycleCharacterizer) and self.world == other.world and self.t_max == other.t_max

@@ -1,6 +1,7 @@
-// forest_core.hpp -- the many-tree search that forest.hip and ../helpforest/helpforest.hip share: one breadth-first tree per map over
-// the records of a KIND (../search/search_logic.hpp: PlainKind, no extra words; ../helpgraph/helpgraph_logic.hpp: HelpKind, two;
-// ../trails/trails_logic.hpp: TrailKind, one), every tree walked depth by depth in the same launches.  Here are the shared kernel
+// forest_core.hpp -- the many-tree search that forest.hip, ../helpforest/helpforest.hip and ../cycleforest/cycleforest.hip share: one
+// breadth-first tree per map over the records of a KIND (../search/search_logic.hpp: PlainKind, no extra words;
+// ../helpgraph/helpgraph_logic.hpp: HelpKind, two; ../trails/trails_logic.hpp: TrailKind, one; ../cycles/cycles_logic.hpp: CycleKind,
+// three or twenty-one), every tree walked depth by depth in the same launches.  Here are the shared kernel
 // parameters, the device bodies of the roots, seed, expand, insert, commit and plans kernels, the handle with its device and pinned
 // buffers, the two halves of a create, the run from judged reset states (counters, seeding, the level loop with the per-map fates of
 // forest_logic.hpp, the plan read-back), and plan / stats / occupancy.  A library keeps its extern "C" functions, its argument checks,
@@ -36,7 +37,6 @@ namespace fl = lle_forest_logic;
 using sd::fail;
 
 constexpr int THREADS = 256;  // lanes of a workgroup of every kernel that runs these bodies
-constexpr int EXTRA_STRIDE = 2;  // words per map of root_extra and goal_extra, whatever the kind's EXTRA
 
 struct Params {  // what every library's kernel parameters begin with
     sl::BatchView b;       // the batch (include/lle_hip.h buffer descriptors, read once)
@@ -55,6 +55,7 @@ struct Params {  // what every library's kernel parameters begin with
     uint64_t cap, slots;
     int64_t n_maps, E, n_lanes;
     int32_t G, seg_words;  // seg_words: word arrays of a map's pool segment (n_words + the library's extra words)
+    int32_t extra_stride;  // words per map of root_extra and goal_extra: the library's extra words, whatever the kind's EXTRA
     uint32_t collect_gems, n_joint;
     int32_t plan_rows;
     // the piece
@@ -84,9 +85,8 @@ __device__ __forceinline__ void seed(const Params& p, const uint32_t* root_extra
     const uint32_t* root = p.roots + m * r.n_words;
     uint32_t* seg = pool_segment(p, m);
     for (int w = 0; w < r.n_words; w++) seg[(uint64_t)w * p.cap] = root[w];
-    sl::ExtraWords<Kind::EXTRA> x{};
-    if constexpr (Kind::EXTRA > 0)  // (the host hands a value over as a lane keeps it between insert and commit: 64 bits, the low word first)
-        x = Kind::words((typename Kind::Value)((uint64_t)root_extra[EXTRA_STRIDE * m] | (uint64_t)root_extra[EXTRA_STRIDE * m + 1] << 32));
+    sl::ExtraWords<Kind::EXTRA> x{};  // (the host hands the words over as the pool stores them)
+    for (int i = 0; i < Kind::EXTRA; i++) x.w[i] = root_extra[(int64_t)p.extra_stride * m + i];
     sl::store_pool_extra(seg, p.cap, r, 0, x);
     const uint64_t h = sl::hash_record(sl::key_with_extra([&](int w) { return root[w]; }, r.n_key, x), r.n_key + Kind::EXTRA);
     p.table[fl::table_base(m, p.slots) + ((uint32_t)h & (uint32_t)(p.slots - 1))] = 0u;
@@ -122,12 +122,12 @@ __device__ __forceinline__ bool insert_front(const Params& p, int64_t k) {
     return !sl::anybody_dead(sl::env_word(p.b, p.lay, k, p.lay.w_bits), p.lay.A);
 }
 
-// The rest of lane k: the value of the kind (of map k / E, as `cell` is), the hash, the probe.  cand_extra[k] keeps a winner's value for
+// The rest of lane k: the value of the kind (of map k / E, as `cell` is), the hash, the probe.  cand[k] keeps a winner's value for
 // the commit (no extra words: unused).  The extra words of a candidate a tag names are worked out again by the comparing lane, from
 // environment map * E + tag and that candidate's own parent in the map's segment (sl::Piece, sl::occupant_is): nothing is handed from
 // lane to lane inside the launch, no lane waits, nothing needs a fence.
 template <class Kind, class Cell>
-__device__ __forceinline__ void insert_back(const Params& p, const Kind& kind, const Cell& cell, uint64_t* cand_extra, int64_t k) {
+__device__ __forceinline__ void insert_back(const Params& p, const Kind& kind, const Cell& cell, typename Kind::Value* cand, int64_t k) {
     const int64_t map = k / p.E;
     const uint32_t local = (uint32_t)(k % p.E);
     unsigned long long* counters = p.counters + fl::counter_index(map, 0);
@@ -150,7 +150,7 @@ __device__ __forceinline__ void insert_back(const Params& p, const Kind& kind, c
                                           sl::TAG_BIT | local, sd::SlotLoad{}, sd::SlotCas{}, same_as);
     if (slot >= 0) {
         p.win_slot[k] = (uint32_t)slot;
-        if constexpr (Kind::EXTRA > 0) cand_extra[k] = value;  // for the commit, a later launch; no lane of this launch reads it
+        if constexpr (Kind::EXTRA > 0) cand[k] = value;  // for the commit, a later launch; no lane of this launch reads it
     } else if (slot == sl::INSERT_FULL) {
         atomicMax(&counters[fl::CNT_OVERFLOW], 1ull);
     }
@@ -160,7 +160,7 @@ __device__ __forceinline__ void insert_back(const Params& p, const Kind& kind, c
 __device__ __forceinline__ bool is_winner(const Params& p, int64_t k) { return k < p.n_lanes && p.valid[k] && p.win_slot[k] != sl::SLOT_EMPTY; }
 
 template <class Kind>
-__device__ __forceinline__ void commit(const Params& p, const Kind& kind, const uint64_t* cand_extra, int64_t k) {
+__device__ __forceinline__ void commit(const Params& p, const Kind& kind, const typename Kind::Value* cand, int64_t k) {
     const uint32_t slot = p.win_slot[k];
     const int64_t map = k / p.E;
     unsigned long long* counters = p.counters + fl::counter_index(map, 0);
@@ -173,7 +173,7 @@ __device__ __forceinline__ void commit(const Params& p, const Kind& kind, const 
     const sl::EnvRecord rec{p.b, r, k};
     uint32_t* seg = pool_segment(p, map);
     typename Kind::Value value{};
-    if constexpr (Kind::EXTRA > 0) value = (typename Kind::Value)cand_extra[k];
+    if constexpr (Kind::EXTRA > 0) value = cand[k];
     sl::copy_record(p.b, r, k, seg, p.cap, idx);
     sl::store_pool_extra(seg, p.cap, r, idx, kind.words(value));
     const uint64_t item = p.piece * (uint64_t)p.E + (uint64_t)(k % p.E);
@@ -195,7 +195,7 @@ __device__ __forceinline__ void plans(const Params& p, uint32_t* goal_extra) {
     uint64_t at = p.desc[m].first_state;
     if constexpr (Kind::EXTRA > 0) {
         const uint32_t* seg = pool_segment(p, m);
-        for (int w = 0; w < Kind::EXTRA; w++) goal_extra[EXTRA_STRIDE * m + w] = at < p.cap ? seg[(uint64_t)(p.lay.n_words + w) * p.cap + at] : 0u;
+        for (int w = 0; w < Kind::EXTRA; w++) goal_extra[(int64_t)p.extra_stride * m + w] = at < p.cap ? seg[(uint64_t)(p.lay.n_words + w) * p.cap + at] : 0u;
     }
     const int64_t length = p.desc[m].items < (uint64_t)p.plan_rows ? (int64_t)p.desc[m].items : (int64_t)p.plan_rows;
     bool ok = true;
@@ -217,12 +217,14 @@ __device__ __forceinline__ void plans(const Params& p, uint32_t* goal_extra) {
 // ================================================================================================ host side
 // What a library's texts and statuses differ by.
 struct Library {
-    const char* prefix;   // of its kernels' names: "forest", "hf"
+    const char* prefix;   // of its kernels' names: "forest", "hf", "cf"
     const char* options;  // the name of its options struct
     const char* search;   // "the search", "the help forest"
     const char* record;   // what it calls a pool entry: "state", "record"
-    int extra;            // word arrays of a map's pool segment behind the record's: 0, or 2 whichever kind runs
-    int capacity_status, dense_status;  // LLE_*_CAPACITY, LLE_TRAILS_DENSE (0: the kind has no walk)
+    int extra;            // word arrays of a map's pool segment behind the record's, and words per map of root_extra and goal_extra: 0; 2
+                          // whichever kind of the help forest runs; 3 or 21 by the agent class of the cycle forest's maps
+    int capacity_status, dense_status;  // LLE_*_CAPACITY, LLE_TRAILS_DENSE / LLE_CYCLES_DENSE (0: the kind has no walk)
+    size_t cand_bytes;    // bytes per lane of the winner buffer between insert and commit: the largest sizeof(Kind::Value) (no extra words: 0)
 };
 
 struct Options {  // a library's options struct, judged
@@ -241,7 +243,7 @@ struct MapRun {  // one map in the last run
     fl::MapProgress progress{};
     std::vector<int64_t> frontier, expanded;
     std::vector<uint8_t> plan;
-    uint32_t extra[EXTRA_STRIDE] = {0u, 0u};  // of the plan's last state (no extra words: unused)
+    uint32_t extra[sl::MAX_EXTRA] = {};  // of the plan's last state (no extra words: unused)
 };
 
 struct Handle {
@@ -259,18 +261,20 @@ struct Handle {
     void* d_static[2] = {nullptr, nullptr};  // the library's static tables
     size_t plans_bytes = 0;
     // a library with extra words
-    uint64_t* d_cand = nullptr;  // [n_lanes]: the extra words of winner k (help value, or the trail value in the low word), for the commit
-    uint32_t *d_root_extra = nullptr, *d_goal_extra = nullptr;  // [n_maps][2]: of every map's reset state in this run, of every solved map's goal
+    void* d_cand = nullptr;  // [n_lanes] of the library's cand_bytes: the value of winner k as its kind keeps it, for the commit
+    uint32_t *d_root_extra = nullptr, *d_goal_extra = nullptr;  // [n_maps][extra]: of every map's reset state in this run, of every solved map's goal
     // pinned: what the host reads and writes once per level, and once per run
     fl::MapDescriptor* h_desc = nullptr;
     uint64_t* h_counters = nullptr;
-    uint32_t* h_extra = nullptr;  // [n_maps][2]: up, the reset states' extra words; down, the goals'
+    uint32_t* h_extra = nullptr;  // [n_maps][extra]: up, the reset states' extra words; down, the goals'
+    int extra = 0;                // the library's extra words
     // the last run
     std::vector<MapRun> maps;
     int64_t valid_items = 0, launched_lanes = 0;
 };
 
-// The kernels of one run (insert: the instantiation it launches) and their bits in the library's kernel name table.
+// The kernels of one run (insert: the instantiation it launches, with `insert_lds` bytes of dynamic LDS) and their bits in the library's
+// kernel name table.
 template <class P>
 struct Launch {
     void (*seed)(P);
@@ -279,6 +283,7 @@ struct Launch {
     void (*commit)(P);
     void (*plans)(P);
     uint32_t seed_bit, piece_bits, plans_bit;
+    size_t insert_lds = 0;
 };
 
 dim3 grid_for(int64_t lanes) { return dim3((unsigned)((lanes + THREADS - 1) / THREADS)); }
@@ -353,9 +358,11 @@ int open(Handle* f, const lle_map* const* maps, int n_maps, const Options& o, co
               hipMalloc(&f->d_counters, M * fl::N_COUNTERS * 8) == hipSuccess && hipMalloc(&f->d_roots, M * (size_t)lay.n_words * 4) == hipSuccess &&
               hipMalloc(&f->d_desc, M * sizeof(fl::MapDescriptor)) == hipSuccess && hipHostMalloc(&f->h_desc, M * sizeof(fl::MapDescriptor)) == hipSuccess &&
               hipHostMalloc(&f->h_counters, M * fl::N_COUNTERS * 8) == hipSuccess;
+    f->extra = lib.extra;
+    const size_t extra_bytes = M * (size_t)lib.extra * 4;
     if (lib.extra > 0)
-        ok = ok && hipMalloc(&f->d_cand, lanes * 8) == hipSuccess && hipMalloc(&f->d_root_extra, M * EXTRA_STRIDE * 4) == hipSuccess &&
-             hipMalloc(&f->d_goal_extra, M * EXTRA_STRIDE * 4) == hipSuccess && hipHostMalloc(&f->h_extra, M * EXTRA_STRIDE * 4) == hipSuccess;
+        ok = ok && hipMalloc(&f->d_cand, lanes * lib.cand_bytes) == hipSuccess && hipMalloc(&f->d_root_extra, extra_bytes) == hipSuccess &&
+             hipMalloc(&f->d_goal_extra, extra_bytes) == hipSuccess && hipHostMalloc(&f->h_extra, extra_bytes) == hipSuccess;
     for (int t = 0; t < 2; t++)
         if (tables[t].bytes > 0)
             ok = ok && hipMalloc(&f->d_static[t], tables[t].bytes) == hipSuccess &&
@@ -384,6 +391,7 @@ int open(Handle* f, const lle_map* const* maps, int n_maps, const Options& o, co
     p->n_lanes = (int64_t)n_maps * o.E;
     p->G = o.info.n_gems;
     p->seg_words = (int32_t)words;
+    p->extra_stride = lib.extra;
     p->n_joint = sl::pow5(o.info.n_agents);
     // ---- every map's reset state (the batch is freshly reset: World::new calls reset)
     f->roots.assign(M * (size_t)lay.n_words, 0u);
@@ -408,9 +416,9 @@ void begin_run(Handle* f, P* p, bool collect_gems) {
         mr.frontier.assign(1, 1);
         mr.expanded.clear();
         mr.plan.clear();
-        std::fill(mr.extra, mr.extra + EXTRA_STRIDE, 0u);
+        std::fill(mr.extra, mr.extra + sl::MAX_EXTRA, 0u);
     }
-    if (f->h_extra) std::fill(f->h_extra, f->h_extra + EXTRA_STRIDE * f->maps.size(), 0u);
+    if (f->h_extra) std::fill(f->h_extra, f->h_extra + (size_t)f->extra * f->maps.size(), 0u);
 }
 
 template <class P>
@@ -420,7 +428,7 @@ int launch_piece(Handle* f, const P& p, const Launch<P>& l, const Library& lib, 
     if (hipGetLastError() != hipSuccess) return fail(LLE_ERR_HIP, std::string(lib.prefix) + "_expand launch failed");
     // (actions in LLE_BUF_ACTIONS; no auto-reset, no sampling, no observation)
     if (lle_batch_step(f->batch, nullptr, LLE_STEP_NO_OBS, 0, 0, 0, f->stream) != LLE_OK) return fail(LLE_ERR_HIP, std::string("lle_batch_step: ") + lle_last_error());
-    hipLaunchKernelGGL(l.insert, grid, block, 0, f->stream, p);
+    hipLaunchKernelGGL(l.insert, grid, block, l.insert_lds, f->stream, p);
     if (hipGetLastError() != hipSuccess) return fail(LLE_ERR_HIP, std::string(lib.prefix) + "_insert launch failed");
     hipLaunchKernelGGL(l.commit, grid, block, 0, f->stream, p);
     if (hipGetLastError() != hipSuccess) return fail(LLE_ERR_HIP, std::string(lib.prefix) + "_commit launch failed");
@@ -461,7 +469,7 @@ int run(Handle* f, P& p, int t_max, const Launch<P>& l, const Library& lib, std:
     // ---- tables, counters and record 0 of every searching map
     bool ok = hipMemsetAsync(p.table, 0xFF, M * (size_t)p.slots * 4, f->stream) == hipSuccess &&
               hipMemcpyAsync(p.counters, f->h_counters, M * fl::N_COUNTERS * 8, hipMemcpyHostToDevice, f->stream) == hipSuccess &&
-              (lib.extra == 0 || hipMemcpyAsync(f->d_root_extra, f->h_extra, M * EXTRA_STRIDE * 4, hipMemcpyHostToDevice, f->stream) == hipSuccess) &&
+              (lib.extra == 0 || hipMemcpyAsync(f->d_root_extra, f->h_extra, M * (size_t)lib.extra * 4, hipMemcpyHostToDevice, f->stream) == hipSuccess) &&
               upload_descriptors(f);
     if (ok) {
         hipLaunchKernelGGL(l.seed, grid_for(f->n_maps), dim3(THREADS), 0, f->stream, p);
@@ -542,7 +550,7 @@ int run(Handle* f, P& p, int t_max, const Launch<P>& l, const Library& lib, std:
             ok = hipGetLastError() == hipSuccess;
         }
         ok = ok && hipMemcpyAsync(host.data(), f->d_plans, bytes, hipMemcpyDeviceToHost, f->stream) == hipSuccess &&
-             (lib.extra == 0 || hipMemcpyAsync(f->h_extra, f->d_goal_extra, M * EXTRA_STRIDE * 4, hipMemcpyDeviceToHost, f->stream) == hipSuccess);
+             (lib.extra == 0 || hipMemcpyAsync(f->h_extra, f->d_goal_extra, M * (size_t)lib.extra * 4, hipMemcpyDeviceToHost, f->stream) == hipSuccess);
         if (hipStreamSynchronize(f->stream) != hipSuccess || !ok) return hip_failed(f, "reading the plans back failed");
         launched.fetch_or(l.plans_bit);
         for (size_t m = 0; m < M; m++) {
@@ -554,7 +562,7 @@ int run(Handle* f, P& p, int t_max, const Launch<P>& l, const Library& lib, std:
             }
             const uint8_t* first = host.data() + m * (size_t)rows * A;
             mr.plan.assign(first, first + (size_t)mr.progress.length * A);
-            for (int w = 0; w < lib.extra; w++) mr.extra[w] = f->h_extra[EXTRA_STRIDE * m + w];
+            for (int w = 0; w < lib.extra; w++) mr.extra[w] = f->h_extra[(size_t)lib.extra * m + w];
         }
     }
     return report(), LLE_OK;

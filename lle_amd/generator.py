@@ -210,7 +210,8 @@ class Divergent(Predicate):
 @dataclass(frozen=True)
 class Interdependent(Predicate):
     """A closed chain of help over `order` agents is required (solve mode 'no-interdependence-N': order 2 is 'no-mutual', answered like
-    `Asymmetric`; N >= 3 is answered by lle_amd.CycleCharacterizer alone, one world at a time: pass it as `characterizer=`)."""
+    `Asymmetric`; N >= 3 is answered by lle_amd.CycleCharacterizer: pass it as `characterizer=` to `is_satisfied_by`, or to
+    `satisfied_by_many` / `generate_n`, where the cycle forest answers for many worlds at once)."""
     order: int = 2
 
     def __post_init__(self):
@@ -344,9 +345,10 @@ class Constraint:
         plain forest (`lle_amd.forest.characterize_many`), which answers Solvable / Independent / Cooperative.
         lle_amd.HelpGraphCharacterizer or lle_amd.TrailCharacterizer: the help forest (`lle_amd.helpforest.characterize_many`),
         which also answers Asymmetric, Convergent, Divergent, Interdependent(2) and -- under TrailCharacterizer -- Sequential(N); every
-        atom costs at most one forest run per shape, made when the first world needs it.  Any other class -- lle_amd.CycleCharacterizer
-        for Interdependent(N >= 3), which the help forest does not answer -- : one such characterizer per world (then `options` go
-        to its Solver)."""
+        atom costs at most one forest run per shape, made when the first world needs it.  lle_amd.CycleCharacterizer: the cycle forest
+        (`lle_amd.cycleforest.characterize_many`), which answers all of those and Interdependent(N) for N >= 3 -- unless `options`
+        holds a key of the single solver (`chunk`, `max_states`): then, and for any other class, one such characterizer per world
+        (`options` go to its Solver)."""
         worlds = list(worlds)
         if characterizer is None:
             from .forest import characterize_many
@@ -357,6 +359,11 @@ class Constraint:
         if characterizer in (HelpGraphCharacterizer, TrailCharacterizer):
             from . import helpforest
             with helpforest.characterize_many(worlds, self.t_max, sequential=characterizer is TrailCharacterizer, **options) as many:
+                return np.array([self._accepts(many.entry(i)) for i in range(len(worlds))], dtype=bool)
+        from .cycles import CycleCharacterizer
+        if characterizer is CycleCharacterizer and not {"chunk", "max_states"} & set(options):
+            from . import cycleforest
+            with cycleforest.characterize_many(worlds, self.t_max, **options) as many:
                 return np.array([self._accepts(many.entry(i)) for i in range(len(worlds))], dtype=bool)
         return np.array([self.is_satisfied_by(w, characterizer=characterizer, **options) for w in worlds], dtype=bool)
 
@@ -370,7 +377,8 @@ def generate_n(n, constraint, *, height, width, n_agents, n_lasers=0, n_gems=0, 
     `mapgen.generate(height, width, n_agents, n_lasers, n_gems, n_exits, wall_fraction, n_voids, seed=seed + i)` for i = 0, 1, ...;
     candidates are drawn `batch` at a time and every batch is filtered by one `constraint.satisfied_by_many` (`options` go there:
     envs_per_map, max_states_per_map, device -- and `characterizer=lle_amd.TrailCharacterizer` or `lle_amd.HelpGraphCharacterizer`
-    for constraints over Asymmetric, Sequential, Convergent, Divergent or Interdependent(2), which the help forest then answers).  The
+    for constraints over Asymmetric, Sequential, Convergent, Divergent or Interdependent(2), which the help forest then answers;
+    `characterizer=lle_amd.CycleCharacterizer` for Interdependent(N) with N >= 3, which the cycle forest answers).  The
     worlds that come out depend on the arguments only, not on `batch`.  Stops after `n` accepted worlds or `max_attempts` candidates
     (None: no limit -- a constraint nothing satisfies then never ends).
 

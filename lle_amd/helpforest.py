@@ -12,7 +12,7 @@ trajectory -- and, per map, exactly the single search: the same lengths, per-dep
         keep = c.is_asymmetric() & ~c.is_sequential(3)
 
 Modes: everything `TrailSolver` serves; "no-cooperation" is answered by an inner `ForestSolver`, "no-interdependence-N" for N >= 3
-raises NotImplementedError.  Which of several shortest plans comes back may differ between runs; lengths and counters do not.  No
+raises NotImplementedError here: the cycle forest (`lle_amd.cycleforest`, over this one) serves it.  Which of several shortest plans comes back may differ between runs; lengths and counters do not.  No
 fallback: a missing library raises.
 """
 import ctypes as C

@@ -45,7 +45,7 @@ struct HfParams : fc::Params {
     const uint32_t* cells;       // [n_maps][H * W]: the sources that own a laser tile on the cell (bit laser_id), per map
     const hl::EdgeRule* rules;   // [n_maps]
     const uint32_t* root_extra;  // [n_maps][2]: the extra words of every map's reset state in this run
-    uint64_t* cand_extra;        // [n_lanes]: the extra words of winner k, for hf_commit
+    void* cand_extra;            // [n_lanes] of 8 bytes: the value of winner k as its kind keeps it, for hf_commit
     uint32_t* goal_extra;        // [n_maps][2]: the extra words of every solved map's goal record
     int32_t H, W;
     int32_t mode, param;
@@ -67,13 +67,13 @@ __global__ __launch_bounds__(fc::THREADS) void hf_expand(HfParams p) { fc::expan
 template <int KIND>
 __global__ __launch_bounds__(fc::THREADS) void hf_insert(HfParams p) {
     const int64_t k = fc::lane();
-    if (fc::insert_front(p, k)) fc::insert_back(p, map_kind<KIND>(p, k / p.E), map_cells(p, k / p.E), p.cand_extra, k);
+    if (fc::insert_front(p, k)) fc::insert_back(p, map_kind<KIND>(p, k / p.E), map_cells(p, k / p.E), static_cast<typename KindOf<KIND>::Value*>(p.cand_extra), k);
 }
 
 template <int KIND>
 __global__ __launch_bounds__(fc::THREADS) void hf_commit(HfParams p) {
     const int64_t k = fc::lane();
-    if (fc::is_winner(p, k)) fc::commit(p, map_kind<KIND>(p, k / p.E), p.cand_extra, k);
+    if (fc::is_winner(p, k)) fc::commit(p, map_kind<KIND>(p, k / p.E), static_cast<const typename KindOf<KIND>::Value*>(p.cand_extra), k);
 }
 
 // (both words of a segment's extra arrays, whichever kind ran: the host knows which of them the kind has)
@@ -97,7 +97,8 @@ std::atomic<uint32_t> g_launched{0};
 enum { K_ROOTS = 0, K_SEED_HELP, K_SEED_TRAIL, K_EXPAND, K_INSERT_HELP, K_INSERT_TRAIL, K_COMMIT_HELP, K_COMMIT_TRAIL, K_PLANS, K_COUNT };
 const char* const KERNEL_NAMES[K_COUNT] = {"hf_roots",         "hf_seed<help>",   "hf_seed<trail>",   "hf_expand", "hf_insert<help>",
                                            "hf_insert<trail>", "hf_commit<help>", "hf_commit<trail>", "hf_plans"};
-const fc::Library LIBRARY = {"hf", "lle_helpforest_options", "the help forest", "record", hfl::EXTRA_WORDS, LLE_HELPGRAPH_CAPACITY, LLE_TRAILS_DENSE};
+const fc::Library LIBRARY = {"hf", "lle_helpforest_options", "the help forest", "record", hfl::EXTRA_WORDS, LLE_HELPGRAPH_CAPACITY, LLE_TRAILS_DENSE,
+                             sizeof(hl::HelpKind::Value)};
 
 // The kernels of a run of kind KIND (in the name table a trail kernel follows its help twin).
 template <int KIND>
@@ -106,7 +107,8 @@ fc::Launch<HfParams> launch_of() {
             1u << K_EXPAND | 1u << (K_INSERT_HELP + KIND) | 1u << (K_COMMIT_HELP + KIND), 1u << K_PLANS};
 }
 
-static_assert(hfl::KIND_HELP == 0 && hfl::KIND_TRAIL == 1 && hfl::EXTRA_WORDS == fc::EXTRA_STRIDE && hl::HelpKind::EXTRA == hfl::EXTRA_WORDS,
+static_assert(hfl::KIND_HELP == 0 && hfl::KIND_TRAIL == 1 && hl::HelpKind::EXTRA == hfl::EXTRA_WORDS && tl::TrailKind::EXTRA <= hfl::EXTRA_WORDS &&
+                  sizeof(tl::TrailKind::Value) <= sizeof(hl::HelpKind::Value),
               "launch_of counts kinds from help = 0; hf_plans fetches a segment's extra arrays as the help kind's words");
 static_assert(LLE_HELPFOREST_MAX_AGENTS == sl::MAX_AGENTS, "include/lle_helpforest.h and search_logic.hpp disagree");
 static_assert(LLE_HELPFOREST_MAX_SOURCES == hl::MAX_SOURCES, "include/lle_helpforest.h and helpgraph_logic.hpp disagree");
@@ -201,7 +203,7 @@ int lle_helpforest_run(lle_helpforest* f, const lle_helpforest_args* args, const
     // ---- every reset state (t = 0: its edges count), judged on the host with the kernels' own functions
     for (size_t m = 0; m < M; m++) {
         fc::MapRun& mr = f->maps[m];
-        uint32_t* extra = f->h_extra + fc::EXTRA_STRIDE * m;
+        uint32_t* extra = f->h_extra + hfl::EXTRA_WORDS * m;
         if (search && !search[m]) {  // not asked for: idle from the first level
             mr.frontier.clear();
             mr.progress = hfl::skipped_progress();
