@@ -27,6 +27,9 @@ def __getattr__(name):
     if name == "TemporalCooperationTracker":  # (is_sequential / is_mutual for a whole batch, liblle_cooptrails.so)
         from .cooptrails import TemporalCooperationTracker
         return TemporalCooperationTracker
+    if name == "ClosedTrailCooperationTracker":  # (is_interdependent(N) for a whole batch, liblle_coopcycles.so)
+        from .coopcycles import ClosedTrailCooperationTracker
+        return ClosedTrailCooperationTracker
     if name in ("Solver", "solve", "SolveMode", "SolverCapacityError"):  # (lle.solver: the exact shortest-plan search, liblle_search.so)
         from . import solver
         return getattr(solver, name)
@@ -71,4 +74,5 @@ __all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorl
            "ForestSolver", "ForestResult", "solve_many", "characterize_many", "Constraint", "WorldFilter", "generate_n",
            "OptimalPolicy", "PolicyCapacityError", "HelpGraphSolver", "HelpGraphCharacterizer", "TrailSolver", "TrailCharacterizer",
            "HelpForestSolver", "HelpForestResult", "ManyHelpCharacterization", "TemporalCooperationTracker",
-           "CycleSolver", "CycleCharacterizer", "CycleForestSolver", "CycleForestResult", "ManyCycleCharacterization"]
+           "CycleSolver", "CycleCharacterizer", "CycleForestSolver", "CycleForestResult", "ManyCycleCharacterization",
+           "ClosedTrailCooperationTracker"]

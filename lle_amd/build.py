@@ -6,7 +6,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def build_native(force=False, verbose=False):
-    """liblle_hip.so (lle_amd/csrc), then the twelve libraries linked against it: liblle_render.so (lle_amd/render: the renderer),
+    """liblle_hip.so (lle_amd/csrc), then the thirteen libraries linked against it: liblle_render.so (lle_amd/render: the renderer),
     liblle_shaping.so (lle_amd/shaping: reward shaping and laser-subgoal extras), liblle_coop.so (lle_amd/coop: cooperation edges
     and episode profiles), liblle_search.so (lle_amd/search: the exact shortest-plan search), liblle_forest.so (lle_amd/forest: that
     search over many maps at once), liblle_policy.so (lle_amd/policy: steps-to-go and expert actions of a whole batch),
@@ -14,11 +14,13 @@ def build_native(force=False, verbose=False):
     (lle_amd/trails: shortest plans without a sequence of N help events), liblle_helpforest.so (lle_amd/helpforest: those two
     searches over many maps at once), liblle_cooptrails.so (lle_amd/cooptrails: the longest help trail of every environment's
     episode, over liblle_coop.so), liblle_cycles.so (lle_amd/cycles: shortest plans without a closed trail of help events over
-    exactly N agents) and liblle_cycleforest.so (lle_amd/cycleforest: that search over many maps at once)."""
+    exactly N agents), liblle_cycleforest.so (lle_amd/cycleforest: that search over many maps at once) and liblle_coopcycles.so
+    (lle_amd/coopcycles: the closed help trails of every environment's episode, over liblle_coop.so and the logic of lle_amd/cycles)."""
     for src, lib in (("csrc", "liblle_hip.so"), ("render", "liblle_render.so"), ("shaping", "liblle_shaping.so"), ("coop", "liblle_coop.so"),
                      ("search", "liblle_search.so"), ("forest", "liblle_forest.so"), ("policy", "liblle_policy.so"),
                      ("helpgraph", "liblle_helpgraph.so"), ("trails", "liblle_trails.so"), ("helpforest", "liblle_helpforest.so"),
-                     ("cooptrails", "liblle_cooptrails.so"), ("cycles", "liblle_cycles.so"), ("cycleforest", "liblle_cycleforest.so")):
+                     ("cooptrails", "liblle_cooptrails.so"), ("cycles", "liblle_cycles.so"), ("cycleforest", "liblle_cycleforest.so"),
+                     ("coopcycles", "liblle_coopcycles.so")):
         cmd = ["make", "-C", os.path.join(_HERE, src), "-j8"] + (["-B"] if force else [])
         res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if verbose or res.returncode != 0:

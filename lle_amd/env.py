@@ -198,13 +198,22 @@ class BatchedLLE:
     (err != 0) marks the unchanged state again, which only counts one more state.  Without the argument the library is not loaded.
     cooperation="temporal": a TemporalCooperationTracker (lle_amd.cooptrails) instead -- everything above plus, by ONE more small launch
     behind the coop launch, the longest trail of help edges in time order that ends at each agent: is_sequential(length), is_mutual,
-    is_interdependent(2), longest_trail().  A refused step adds no state to the trails; reset and set_state do as above."""
+    is_interdependent(2), longest_trail().  A refused step adds no state to the trails; reset and set_state do as above.
+    cooperation="closed-trails": a ClosedTrailCooperationTracker (lle_amd.coopcycles) -- everything above plus, by ONE more small launch
+    behind the trails launch, the set of (anchor, current, support) triples of the episode's help trails: is_interdependent(n_agents)
+    for 2 <= n_agents <= 6, closed_orders().  Maps of at most 6 agents; more is a ValueError."""
 
     def __init__(self, maps, n_envs, obs_type="layered", state_type="state", walkable_lasers=True, randomize_lasers=False,
                  multi_objective=False, death_strategy="end", padding_size=0, device=None, seed=0, name=None, incremental_obs=False, obs_dtype=None,
                  reward_strategy=None, extras_generator=None, cooperation=False):
-        if isinstance(cooperation, str) and cooperation != "temporal":
-            raise ValueError(f"cooperation: True, False or \"temporal\", got {cooperation!r}")
+        if isinstance(cooperation, str) and cooperation not in ("temporal", "closed-trails"):
+            raise ValueError(f"cooperation: True, False, \"temporal\" or \"closed-trails\", got {cooperation!r}")
+        if cooperation == "closed-trails":  # (refused before anything is put on the device)
+            first = maps[0] if isinstance(maps, (list, tuple)) else maps
+            n_agents = (first if isinstance(first, _capi.Map) else _capi.Map(first)).n_agents
+            if n_agents > 6:
+                raise ValueError(f"cooperation=\"closed-trails\" serves maps of at most 6 agents, this one has {n_agents}; "
+                                 "cooperation=\"temporal\" serves any map")
         if death_strategy == "respawn":
             raise NotImplementedError("Respawn strategy is not implemented yet")  # env.py:106-107
         if death_strategy != "end":
@@ -283,7 +292,10 @@ class BatchedLLE:
         if cooperation:
             from . import cooperation as coop
             self._coop_ops = coop
-            if isinstance(cooperation, str):
+            if cooperation == "closed-trails":
+                from .coopcycles import ClosedTrailCooperationTracker
+                self.cooperation = ClosedTrailCooperationTracker(self.world)
+            elif isinstance(cooperation, str):
                 from .cooptrails import TemporalCooperationTracker
                 self.cooperation = TemporalCooperationTracker(self.world)
             else:
