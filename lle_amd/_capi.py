@@ -8,6 +8,8 @@ of anything that needs it raises.
 import ctypes as C
 import os
 
+from . import _binding
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LLE_HIP_LIB") or os.path.join(_HERE, "liblle_hip.so")  # override: A/B runs of two builds
 
@@ -275,21 +277,14 @@ def lib():
     return L
 
 
-def _debug_names(fn):
-    need = fn(None, 0)
-    buf = C.create_string_buffer(need)
-    fn(buf, need)
-    return [n for n in buf.value.decode().split("\n") if n]
-
-
 def launched_kernels():
     """Names of the kernel instantiations this process has launched so far (lle_debug_launched)."""
-    return _debug_names(lib().lle_debug_launched)
+    return _binding.names(lib().lle_debug_launched)
 
 
 def reachable_kernels():
     """Names of every kernel instantiation the launchers' dispatch can reach (lle_debug_reachable)."""
-    return _debug_names(lib().lle_debug_reachable)
+    return _binding.names(lib().lle_debug_reachable)
 
 
 def refresh_tuning():

@@ -22,6 +22,9 @@
 #include <vector>
 
 #include "../../include/lle_coop.h"
+#include "tracker_core.hpp"
+
+namespace eo = lle_episode_ops;
 
 namespace lle {
 
@@ -108,8 +111,7 @@ __global__ __launch_bounds__(COOP_THREADS) void coop_kernel(CoopParams p) {
     if (p.env_mask && p.env_mask[env] == 0) return;
     const int64_t map = env / p.envs_per_map;
     const bool agent = a < p.A;  // lanes A .. G-1 of a group carry no agent: their words are zero
-    const bool was_reset = (p.flags & LLE_COOP_HONOUR_AUTO_RESET) && (p.evcount[env] & 0x80u);
-    const uint32_t reset_ops = was_reset ? (uint32_t)(LLE_COOP_FINISH | LLE_COOP_CLEAR | LLE_COOP_MARK_STARTS) : 0u;
+    const uint32_t reset_ops = eo::reset_ops(p.flags, p.evcount + env);
     if ((p.ops | reset_ops) == 0u) return;
     const int64_t idx = env * p.A + a;
 
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(COOP_THREADS) void coop_kernel(CoopParams p) {
         }
     }
 
-    // ---- the operations: the auto-reset's first, then the caller's
+    // ---- the operations: the auto-reset's first, then the caller's whole (no SKIP_REFUSED here: stages 1 and 2 of episode_ops.hpp as one)
     uint32_t episode = 0u, last = 0u;
     uint32_t count = 0u, last_count = 0u;
     bool finished = false;
@@ -161,7 +163,7 @@ __global__ __launch_bounds__(COOP_THREADS) void coop_kernel(CoopParams p) {
     const uint32_t step_any = group_or<G>(step);
 #pragma unroll
     for (int phase = 0; phase < 2; phase++) {
-        const uint32_t ops = phase == 0 ? reset_ops : p.ops;
+        const uint32_t ops = phase == 0 ? eo::stage_ops(reset_ops, p.ops, 0) : eo::stage_ops(reset_ops, p.ops, 1) | eo::stage_ops(reset_ops, p.ops, 2);
         if (ops & LLE_COOP_FINISH) { last = episode; last_count = count; finished = true; }
         if (ops & LLE_COOP_CLEAR) { episode = 0u; count = 0u; }
         if (ops & LLE_COOP_MARK_STARTS) { episode |= start; count = min(255u, count + (start_any ? 1u : 0u)); }
@@ -196,20 +198,19 @@ LLE_COOP_INSTANTIATE(16)
 
 // ================================================================================================ host side
 using lle::CoopParams;
+using namespace lle_abi_host;
+
+static_assert(LLE_COOP_FINISH == eo::FINISH && LLE_COOP_CLEAR == eo::CLEAR && LLE_COOP_MARK_STARTS == eo::MARK_STARTS && LLE_COOP_MARK_POS == eo::MARK_POS &&
+                  LLE_COOP_HONOUR_AUTO_RESET == eo::HONOUR_AUTO_RESET,
+              "the shared decode reads this header's values");
 
 namespace {
 
-thread_local std::string g_error;
 std::atomic<uint32_t> g_launched{0};
 // bit 2 * log2(G) + LDS_TABLE
 const char* const KERNEL_NAMES[10] = {"coop_kernel<1,false>", "coop_kernel<1,true>",  "coop_kernel<2,false>",  "coop_kernel<2,true>",
                                       "coop_kernel<4,false>", "coop_kernel<4,true>",  "coop_kernel<8,false>",  "coop_kernel<8,true>",
                                       "coop_kernel<16,false>", "coop_kernel<16,true>"};
-
-int fail(int code, const std::string& why) {
-    g_error = why;
-    return code;
-}
 
 struct MapTables {
     int32_t H = 0, W = 0, A = 0, n_sources = 0;
@@ -260,30 +261,6 @@ bool build_map(const lle_map* map, MapTables& mt, std::string& err) {
     }
     mt.starts.assign(lle::START_PITCH, 0u);
     return true;
-}
-
-struct DeviceGuard {  // the handle's device current for the call, the caller's put back
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-size_t names_out(uint32_t bits, char* buf, size_t cap) {
-    std::string s;
-    for (int k = 0; k < 10; k++)
-        if ((bits >> k) & 1u) s += std::string(KERNEL_NAMES[k]) + "\n";
-    if (buf && cap > 0) {
-        const size_t n = std::min(cap - 1, s.size());
-        std::memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return s.size() + 1;
 }
 
 // One launch of coop_kernel<1 << log2_g, lds_table> over p.n_envs environments.
@@ -488,13 +465,9 @@ lle_coop* lle_coop_create(lle_batch* batch, const lle_map* const* maps, int n_ma
     std::vector<uint32_t> tables;
     for (const auto& m : c->maps) tables.insert(tables.end(), m.cells.begin(), m.cells.end());
     // the five arrays, each starting on a 256-byte boundary between runs of LLE_COOP_GUARD_BYTES zero bytes that no launch writes
-    const size_t guard = LLE_COOP_GUARD_BYTES;
     const size_t sizes[LLE_COOP_BUF_COUNT] = {nA * 4, nA * 4, nA * 4, n * 8, n * 8};
-    size_t offsets[LLE_COOP_BUF_COUNT], state_bytes = guard;
-    for (int k = 0; k < LLE_COOP_BUF_COUNT; k++) {
-        offsets[k] = state_bytes;
-        state_bytes += (sizes[k] + guard - 1) / guard * guard + guard;
-    }
+    size_t offsets[LLE_COOP_BUF_COUNT];
+    const size_t state_bytes = eo::guarded_layout(sizes, LLE_COOP_BUF_COUNT, LLE_COOP_GUARD_BYTES, offsets);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (hipMalloc(&c->d_tables, std::max<size_t>(4, tables.size() * 4)) != hipSuccess ||
         hipMalloc(&c->d_starts, (size_t)n_maps * lle::START_PITCH * 4) != hipSuccess ||
@@ -588,11 +561,8 @@ int lle_coop_start_edges(const lle_coop* c, int map_index, uint32_t* out, int ca
 }
 
 int lle_coop_update(lle_coop* c, const lle_coop_update_args* args, void* stream) {
-    if (!c || !args) return fail(LLE_ERR_NULL, "NULL handle or arguments");
-    if (args->struct_bytes != sizeof(lle_coop_update_args)) return fail(LLE_ERR_ARG, "lle_coop_update_args.struct_bytes is not sizeof(lle_coop_update_args)");
-    const uint32_t all_ops = LLE_COOP_FINISH | LLE_COOP_CLEAR | LLE_COOP_MARK_STARTS | LLE_COOP_MARK_POS;
-    const uint32_t all_flags = LLE_COOP_HONOUR_AUTO_RESET | LLE_COOP_ENV_SOURCES;
-    if ((args->ops & ~all_ops) || (args->flags & ~all_flags)) return fail(LLE_ERR_ARG, "unknown operation or flag");
+    const int rc = lle_tracker_core::check_update_args(c, args, "lle_coop_update_args", LLE_COOP_HONOUR_AUTO_RESET | LLE_COOP_ENV_SOURCES);
+    if (rc != LLE_OK) return rc;
     if ((args->flags & LLE_COOP_ENV_SOURCES) && c->any_start_on_beam && ((args->ops & LLE_COOP_MARK_STARTS) || (args->flags & LLE_COOP_HONOUR_AUTO_RESET)))
         return fail(LLE_ERR_ARG, "a start cell of the map lies on a laser cell and the batch has per-environment sources: the start edges depend on "
                                  "each environment's colours.  Reset through env_mask and send FINISH | CLEAR | MARK_POS on the reset state instead of "
@@ -605,7 +575,7 @@ int lle_coop_update(lle_coop* c, const lle_coop_update_args* args, void* stream)
     return launch(p, c->log2_g, c->lds_table, reinterpret_cast<hipStream_t>(stream));
 }
 
-size_t lle_coop_debug_launched(char* buf, size_t cap) { return names_out(g_launched.load(), buf, cap); }
-size_t lle_coop_debug_compiled(char* buf, size_t cap) { return names_out(0x3FFu, buf, cap); }
+size_t lle_coop_debug_launched(char* buf, size_t cap) { return names_out(KERNEL_NAMES, 10, g_launched.load(), buf, cap); }
+size_t lle_coop_debug_compiled(char* buf, size_t cap) { return names_out(KERNEL_NAMES, 10, 0x3FFu, buf, cap); }
 
 }  // extern "C"

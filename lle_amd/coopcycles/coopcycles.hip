@@ -14,22 +14,21 @@
 // only when the walk stayed within its budget; a further layer of the same launch reads it back from there.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <atomic>
 #include <cstdint>
-#include <cstring>
 #include <string>
-#include <vector>
 
 #include "../../include/lle_coopcycles.h"
+#include "../coop/tracker_core.hpp"
 #include "../cycles/cycles_logic.hpp"
+
+namespace cl = lle_cycles_logic;
+namespace eo = lle_episode_ops;
 
 namespace lle {
 
-namespace cl = lle_cycles_logic;
-
 constexpr int COOPCYCLES_THREADS = 256;
-constexpr int START_PITCH = 16;  // per map: the start edges of every agent (lle_coop_start_edges)
+using lle_tracker_core::START_PITCH;  // per map: the start edges of every agent
 
 static_assert(LLE_COOPCYCLES_MAX_AGENTS == cl::sl::MAX_AGENTS && LLE_COOPCYCLES_WALK_BUDGET == cl::WALK_BUDGET, "the header's constants");
 static_assert(LLE_COOPCYCLES_SMALL_WORDS == cl::SMALL_WORDS && LLE_COOPCYCLES_LARGE_WORDS == cl::LARGE_WORDS, "the header's constants");
@@ -59,9 +58,6 @@ struct EpisodeWords {
     __host__ __device__ uint32_t operator()(int i) const { return empty ? 0u : base[(int64_t)i * stride]; }
 };
 
-// Row h of a layer, cleaned by the rule of lle_cooptrails_logic::clean_row: no self-loop, no agent the map lacks.
-__device__ __forceinline__ uint32_t clean_row(uint32_t row, int h, int A) { return row & ((1u << A) - 1u) & ~(1u << h) & 0xFFFFu; }
-
 // The closed orders of a value as a bit set: bit k = some (a, a, S) with |S| = k.
 template <int W, class Read>
 __device__ uint32_t closed_orders(const Read& words, int A, const uint64_t* of_size) {
@@ -80,19 +76,17 @@ __global__ __launch_bounds__(COOPCYCLES_THREADS) void coopcycles_kernel(CoopCycl
     // (no barrier and no cross-lane read in this kernel: a lane may leave at any point)
     if (env >= p.n_envs) return;
     if (p.env_mask && p.env_mask[env] == 0) return;
-    const bool was_reset = (p.flags & LLE_COOPCYCLES_HONOUR_AUTO_RESET) && (p.evcount[env] & 0x80u);
-    const uint32_t reset_ops = was_reset ? (uint32_t)(LLE_COOPCYCLES_FINISH | LLE_COOPCYCLES_CLEAR | LLE_COOPCYCLES_MARK_STARTS) : 0u;
+    const uint32_t reset_ops = eo::reset_ops(p.flags, p.evcount + env);
     if ((p.ops | reset_ops) == 0u) return;
-    const bool refused = (p.flags & LLE_COOPCYCLES_SKIP_REFUSED) && p.err[env] != 0;
-    const uint32_t own_ops = refused ? p.ops & ~(uint32_t)LLE_COOPCYCLES_MARK_POS : p.ops;
+    const uint32_t own_ops = eo::own_ops(p.ops, p.flags, p.err + env);
     const int A = p.A;
 
     // ---- the arc words of both layers: bit 8 h + b = h helps b
     uint64_t step = 0ull, start = 0ull;
     if (own_ops & LLE_COOPCYCLES_MARK_POS)
-        for (int h = 0; h < A; h++) step |= (uint64_t)clean_row(p.step_edges[env * A + h], h, A) << (8 * h);
+        for (int h = 0; h < A; h++) step |= (uint64_t)eo::clean_row(p.step_edges[env * A + h], h, A) << (8 * h);
     if ((own_ops | reset_ops) & LLE_COOPCYCLES_MARK_STARTS)
-        for (int h = 0; h < A; h++) start |= (uint64_t)clean_row(p.starts[(env / p.envs_per_map) * START_PITCH + h], h, A) << (8 * h);
+        for (int h = 0; h < A; h++) start |= (uint64_t)eo::clean_row(p.starts[(env / p.envs_per_map) * START_PITCH + h], h, A) << (8 * h);
 
     // ---- the lane's own words for the value a layer builds
     cl::Words out;
@@ -113,8 +107,8 @@ __global__ __launch_bounds__(COOPCYCLES_THREADS) void coopcycles_kernel(CoopCycl
 
     // ---- the operations: the auto-reset's, then the caller's; stage 2 is the caller's MARK_POS (one walk in the code, not three)
 #pragma unroll 1
-    for (int stage = 0; stage < 3; stage++) {
-        const uint32_t ops = stage == 0 ? reset_ops : stage == 1 ? own_ops & ~(uint32_t)LLE_COOPCYCLES_MARK_POS : own_ops & (uint32_t)LLE_COOPCYCLES_MARK_POS;
+    for (int stage = 0; stage < eo::STAGES; stage++) {
+        const uint32_t ops = eo::stage_ops(reset_ops, own_ops, stage);
         if (ops & LLE_COOPCYCLES_FINISH) {
             for (int i = 0; i < W; i++) last[(int64_t)i * p.n_envs] = cleared ? 0u : episode[(int64_t)i * p.n_envs];
             p.last_cprofile[env] = orders | count << 8 | dense << 16 | valid;
@@ -149,45 +143,25 @@ template __global__ void coopcycles_kernel<cl::LARGE_WORDS>(CoopCyclesParams);
 
 }  // namespace lle
 
-// ================================================================================================ host side
+// ================================================================================================ host side (../coop/tracker_core.hpp)
 using lle::CoopCyclesParams;
-namespace cl = lle_cycles_logic;
+using namespace lle_abi_host;
+namespace tc = lle_tracker_core;
+
+static_assert(LLE_COOPCYCLES_FINISH == eo::FINISH && LLE_COOPCYCLES_CLEAR == eo::CLEAR && LLE_COOPCYCLES_MARK_STARTS == eo::MARK_STARTS &&
+                  LLE_COOPCYCLES_MARK_POS == eo::MARK_POS && LLE_COOPCYCLES_HONOUR_AUTO_RESET == eo::HONOUR_AUTO_RESET &&
+                  LLE_COOPCYCLES_SKIP_REFUSED == eo::SKIP_REFUSED && LLE_COOPCYCLES_BUF_COUNT == tc::N_ARRAYS,
+              "the shared decode and the shared handle read this header's values");
+
+struct lle_coopcycles : tc::Tracker<CoopCyclesParams> {
+    int words = 0;
+};
 
 namespace {
 
-thread_local std::string g_error;
 std::atomic<uint32_t> g_launched{0};
 // bit 0: W = 3, bit 1: W = 21
 const char* const KERNEL_NAMES[2] = {"coopcycles_kernel<3>", "coopcycles_kernel<21>"};
-
-int fail(int code, const std::string& why) {
-    g_error = why;
-    return code;
-}
-
-struct DeviceGuard {  // the handle's device current for the call, the caller's put back
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-size_t names_out(uint32_t bits, char* buf, size_t cap) {
-    std::string s;
-    for (int k = 0; k < 2; k++)
-        if ((bits >> k) & 1u) s += std::string(KERNEL_NAMES[k]) + "\n";
-    if (buf && cap > 0) {
-        const size_t n = std::min(cap - 1, s.size());
-        std::memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return s.size() + 1;
-}
 
 // One launch of coopcycles_kernel<words> over p.n_envs environments.
 int launch(const CoopCyclesParams& p, int words, hipStream_t st) {
@@ -201,31 +175,11 @@ int launch(const CoopCyclesParams& p, int words, hipStream_t st) {
     return LLE_OK;
 }
 
-}  // namespace
-
-struct lle_coopcycles {
-    int device = 0;
-    int n_maps = 0;
-    int words = 0;
-    const lle_coop* coop = nullptr;
-    uint32_t* d_starts = nullptr;
-    uint8_t* d_state = nullptr;  // the four arrays between guard bytes
-    CoopCyclesParams p{};
-};
-
-namespace {
-
-// The start edges of map `m` from the coop handle to the device (synchronises `st`).
-int upload_starts(lle_coopcycles* t, int m, hipStream_t st) {
-    uint32_t rows[lle::START_PITCH] = {0};
-    const int A = lle_coop_start_edges(t->coop, m, rows, lle::START_PITCH);
-    if (A != t->p.A) return fail(LLE_ERR_ARG, std::string("lle_coop_start_edges: ") + (A < 0 ? lle_coop_last_error() : "another number of agents"));
-    if (hipMemcpyAsync(t->d_starts + (size_t)m * lle::START_PITCH, rows, sizeof(rows), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(LLE_ERR_HIP, "uploading the start edges failed");
-    }
-    return LLE_OK;
+// The refusal of a map with more agents than a value holds.  [[clang::noinline]] here and on masks_of_size below: the calls stay out
+// of line, so that the library's dynamic symbols (those weak instantiations among them) are the ones it had when create was one function.
+std::string too_many_agents(int A) {
+    [[clang::noinline]] return "the closed-trail tracker serves maps of at most " + std::to_string(LLE_COOPCYCLES_MAX_AGENTS) +
+                               " agents, this one has " + std::to_string(A) + ": a packed set of agent masks is one 64-bit word";
 }
 
 }  // namespace
@@ -234,133 +188,37 @@ extern "C" {
 
 const char* lle_coopcycles_last_error(void) { return g_error.c_str(); }
 
-void lle_coopcycles_free(lle_coopcycles* t) {
-    if (!t) return;
-    DeviceGuard g(t->device);
-    (void)hipFree(t->d_starts);
-    (void)hipFree(t->d_state);
-    delete t;
-}
+void lle_coopcycles_free(lle_coopcycles* t) { tc::destroy(t); }
 
 lle_coopcycles* lle_coopcycles_create(lle_batch* batch, lle_coop* coop, void* stream) {
-    int n_devices = 0;
-    if (hipGetDeviceCount(&n_devices) != hipSuccess || n_devices <= 0) {
-        (void)hipGetLastError();
-        fail(LLE_ERR_NO_DEVICE, "no HIP device: the closed-trail cooperation tracker runs on the GPU only (there is no CPU fallback)");
-        return nullptr;
-    }
-    if (!batch || !coop) {
-        fail(LLE_ERR_NULL, "NULL batch or coop handle");
-        return nullptr;
-    }
-    lle_buffer_desc evcount{}, err{};
-    if (lle_batch_get_buffer(batch, LLE_BUF_EVCOUNT, &evcount) || lle_batch_get_buffer(batch, LLE_BUF_ERR, &err)) {
-        fail(LLE_ERR_ARG, "lle_batch_get_buffer failed");
-        return nullptr;
-    }
-    void* step_edges = lle_coop_buffer(coop, LLE_COOP_STEP_EDGES);
-    const int A = lle_coop_start_edges(coop, 0, nullptr, 0);
-    const int n_maps = lle_batch_n_maps(batch);
-    const int64_t n = lle_batch_n_envs(batch);
-    if (!step_edges || A < 1 || n_maps <= 0 || n <= 0 || n % n_maps != 0) {
-        fail(LLE_ERR_ARG, "the coop handle or the batch is not usable (agents, maps or environments out of range)");
-        return nullptr;
-    }
-    if (A > LLE_COOPCYCLES_MAX_AGENTS) {
-        fail(LLE_ERR_UNSUPPORTED, "the closed-trail tracker serves maps of at most " + std::to_string(LLE_COOPCYCLES_MAX_AGENTS) + " agents, this one has " +
-                                      std::to_string(A) + ": a packed set of agent masks is one 64-bit word");
-        return nullptr;
-    }
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, step_edges) != hipSuccess) {
-        (void)hipGetLastError();
-        fail(LLE_ERR_HIP, "the coop handle's arrays are not device memory");
-        return nullptr;
-    }
-    auto* t = new lle_coopcycles();
-    t->device = attr.device;
-    t->n_maps = n_maps;
-    t->coop = coop;
+    auto* t = tc::bind<lle_coopcycles>(batch, coop, "no HIP device: the closed-trail cooperation tracker runs on the GPU only (there is no CPU fallback)",
+                                       tc::AgentLimit{LLE_COOPCYCLES_MAX_AGENTS, too_many_agents});
+    if (!t) return nullptr;
+    const int A = t->p.A;
+    const size_t value_bytes = 4 * (size_t)cl::words_of(A);
+    if (!tc::allocate(t, {value_bytes, value_bytes, 4, 4}, "allocating the coopcycles arrays failed", stream)) return nullptr;
     t->words = cl::words_of(A);
-    DeviceGuard g(t->device);
-    // the four arrays, each starting on a 256-byte boundary between runs of LLE_COOP_GUARD_BYTES zero bytes that no launch writes
-    const size_t guard = LLE_COOP_GUARD_BYTES;
-    const size_t sizes[LLE_COOPCYCLES_BUF_COUNT] = {(size_t)n * 4 * (size_t)t->words, (size_t)n * 4 * (size_t)t->words, (size_t)n * 4, (size_t)n * 4};
-    size_t offsets[LLE_COOPCYCLES_BUF_COUNT], state_bytes = guard;
-    for (int k = 0; k < LLE_COOPCYCLES_BUF_COUNT; k++) {
-        offsets[k] = state_bytes;
-        state_bytes += (sizes[k] + guard - 1) / guard * guard + guard;
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const size_t start_bytes = (size_t)n_maps * lle::START_PITCH * 4;
-    if (hipMalloc(&t->d_starts, start_bytes) != hipSuccess || hipMalloc(&t->d_state, state_bytes) != hipSuccess ||
-        hipMemsetAsync(t->d_starts, 0, start_bytes, st) != hipSuccess || hipMemsetAsync(t->d_state, 0, state_bytes, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError();
-        fail(LLE_ERR_HIP, "allocating the coopcycles arrays failed");
-        lle_coopcycles_free(t);
-        return nullptr;
-    }
     CoopCyclesParams& p = t->p;
-    p.step_edges = static_cast<const uint32_t*>(step_edges);
-    p.starts = t->d_starts;
-    p.evcount = static_cast<const uint8_t*>(evcount.ptr);
-    p.err = static_cast<const uint8_t*>(err.ptr);
-    p.episode_closed = reinterpret_cast<uint32_t*>(t->d_state + offsets[LLE_COOPCYCLES_EPISODE_CLOSED]);
-    p.last_closed = reinterpret_cast<uint32_t*>(t->d_state + offsets[LLE_COOPCYCLES_LAST_CLOSED]);
-    p.episode_cprofile = reinterpret_cast<uint32_t*>(t->d_state + offsets[LLE_COOPCYCLES_EPISODE_CPROFILE]);
-    p.last_cprofile = reinterpret_cast<uint32_t*>(t->d_state + offsets[LLE_COOPCYCLES_LAST_CPROFILE]);
-    p.n_envs = n;
-    p.envs_per_map = n / n_maps;
-    p.A = A;
+    p.episode_closed = reinterpret_cast<uint32_t*>(t->arrays[LLE_COOPCYCLES_EPISODE_CLOSED]);
+    p.last_closed = reinterpret_cast<uint32_t*>(t->arrays[LLE_COOPCYCLES_LAST_CLOSED]);
+    p.episode_cprofile = reinterpret_cast<uint32_t*>(t->arrays[LLE_COOPCYCLES_EPISODE_CPROFILE]);
+    p.last_cprofile = reinterpret_cast<uint32_t*>(t->arrays[LLE_COOPCYCLES_LAST_CPROFILE]);
     p.order = cl::Order{A, ~0ull, 0ull};  // N = the map's agents, every mask allowed, none "exact": no pruning, no closing
-    for (int k = 0; k <= cl::MAX_ORDER; k++) p.of_size[k] = cl::masks_of_size(k);
-    for (int m = 0; m < n_maps; m++) {
-        if (upload_starts(t, m, st) != LLE_OK) {
-            lle_coopcycles_free(t);
-            return nullptr;
-        }
-    }
-    g_error.clear();
+    for (int k = 0; k <= cl::MAX_ORDER; k++) [[clang::noinline]] p.of_size[k] = cl::masks_of_size(k);
     return t;
 }
 
-int lle_coopcycles_update_map(lle_coopcycles* t, int map_index, void* stream) {
-    if (!t) return fail(LLE_ERR_NULL, "NULL handle");
-    if (map_index < 0 || map_index >= t->n_maps) return fail(LLE_ERR_ARG, "map_index out of range");
-    DeviceGuard g(t->device);
-    return upload_starts(t, map_index, reinterpret_cast<hipStream_t>(stream));
-}
+int lle_coopcycles_update_map(lle_coopcycles* t, int map_index, void* stream) { return tc::update_map(t, map_index, stream); }
 
 void* lle_coopcycles_buffer(lle_coopcycles* t, int which) {
-    if (!t || which < 0 || which >= LLE_COOPCYCLES_BUF_COUNT) {
-        fail(LLE_ERR_ARG, "NULL handle or `which` not one of LLE_COOPCYCLES_EPISODE_CLOSED ... LLE_COOPCYCLES_LAST_CPROFILE");
-        return nullptr;
-    }
-    switch (which) {
-        case LLE_COOPCYCLES_EPISODE_CLOSED: return t->p.episode_closed;
-        case LLE_COOPCYCLES_LAST_CLOSED: return t->p.last_closed;
-        case LLE_COOPCYCLES_EPISODE_CPROFILE: return t->p.episode_cprofile;
-        default: return t->p.last_cprofile;
-    }
+    return tc::buffer(t, which, "NULL handle or `which` not one of LLE_COOPCYCLES_EPISODE_CLOSED ... LLE_COOPCYCLES_LAST_CPROFILE");
 }
 
 int lle_coopcycles_update(lle_coopcycles* t, const lle_coopcycles_update_args* args, void* stream) {
-    if (!t || !args) return fail(LLE_ERR_NULL, "NULL handle or arguments");
-    if (args->struct_bytes != sizeof(lle_coopcycles_update_args))
-        return fail(LLE_ERR_ARG, "lle_coopcycles_update_args.struct_bytes is not sizeof(lle_coopcycles_update_args)");
-    const uint32_t all_ops = LLE_COOPCYCLES_FINISH | LLE_COOPCYCLES_CLEAR | LLE_COOPCYCLES_MARK_STARTS | LLE_COOPCYCLES_MARK_POS;
-    const uint32_t all_flags = LLE_COOPCYCLES_HONOUR_AUTO_RESET | LLE_COOPCYCLES_SKIP_REFUSED;
-    if ((args->ops & ~all_ops) || (args->flags & ~all_flags)) return fail(LLE_ERR_ARG, "unknown operation or flag");
-    CoopCyclesParams p = t->p;
-    p.ops = args->ops;
-    p.flags = args->flags;
-    p.env_mask = args->env_mask;
-    DeviceGuard g(t->device);
-    return launch(p, t->words, reinterpret_cast<hipStream_t>(stream));
+    return tc::update(t, args, "lle_coopcycles_update_args", stream, [t](const CoopCyclesParams& p, hipStream_t st) { return launch(p, t->words, st); });
 }
 
-size_t lle_coopcycles_debug_launched(char* buf, size_t cap) { return names_out(g_launched.load(), buf, cap); }
-size_t lle_coopcycles_debug_compiled(char* buf, size_t cap) { return names_out(0x3u, buf, cap); }
+size_t lle_coopcycles_debug_launched(char* buf, size_t cap) { return names_out(KERNEL_NAMES, 2, g_launched.load(), buf, cap); }
+size_t lle_coopcycles_debug_compiled(char* buf, size_t cap) { return names_out(KERNEL_NAMES, 2, 0x3u, buf, cap); }
 
 }  // extern "C"

@@ -17,7 +17,8 @@ import ctypes as C
 import os
 import weakref
 
-from . import _capi
+from . import _binding, _capi
+from ._binding import UpdateArgs  # lle_coop_update_args
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblle_coop.so")
@@ -33,11 +34,6 @@ EXPORTS = ["lle_coop_cell_masks", "lle_coop_create", "lle_coop_update_map", "lle
            "lle_coop_start_edges", "lle_coop_last_error", "lle_coop_debug_launched", "lle_coop_debug_compiled"]
 
 
-class UpdateArgs(C.Structure):
-    """lle_coop_update_args."""
-    _fields_ = [("struct_bytes", C.c_uint32), ("ops", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32), ("env_mask", C.c_void_p)]
-
-
 _lib = None
 
 
@@ -47,39 +43,18 @@ def lib():
     if _lib is not None:
         return _lib
     _capi.lib()
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`.  "
-                          "lle_amd has no fallback for the cooperation tracker.")
-    L = C.CDLL(LIB_PATH)
+    L = _binding.load(LIB_PATH, "the cooperation tracker")
     vp, i32 = C.c_void_p, C.c_int
+    _binding.tracker_signatures(L, "lle_coop", [vp, C.POINTER(vp), i32, vp], [vp, i32, vp, vp])
     L.lle_coop_cell_masks.restype = i32
     L.lle_coop_cell_masks.argtypes = [vp, C.POINTER(C.c_uint32), i32]
-    L.lle_coop_create.restype = vp
-    L.lle_coop_create.argtypes = [vp, C.POINTER(vp), i32, vp]
-    L.lle_coop_update_map.restype = i32
-    L.lle_coop_update_map.argtypes = [vp, i32, vp, vp]
-    L.lle_coop_free.restype = None
-    L.lle_coop_free.argtypes = [vp]
-    L.lle_coop_update.restype = i32
-    L.lle_coop_update.argtypes = [vp, C.POINTER(UpdateArgs), vp]
-    L.lle_coop_buffer.restype = vp
-    L.lle_coop_buffer.argtypes = [vp, i32]
     L.lle_coop_start_edges.restype = i32
     L.lle_coop_start_edges.argtypes = [vp, i32, C.POINTER(C.c_uint32), i32]
-    L.lle_coop_last_error.restype = C.c_char_p
-    L.lle_coop_last_error.argtypes = []
-    for fn in (L.lle_coop_debug_launched, L.lle_coop_debug_compiled):
-        fn.restype = C.c_size_t
-        fn.argtypes = [C.c_char_p, C.c_size_t]
     _lib = L
     return L
 
 
-def _names(fn):
-    need = fn(None, 0)
-    buf = C.create_string_buffer(need)
-    fn(buf, need)
-    return [n for n in buf.value.decode().split("\n") if n]
+_names = _binding.names  # (other modules and tests take it from here)
 
 
 def launched_kernels():
@@ -137,18 +112,10 @@ class CooperationTracker:
         w._coop_trackers.add(self)  # update_map / update_sources of the world refresh the tracker's tables
 
     def _view(self, which, shape, typestr):
-        import torch
-        ptr = lib().lle_coop_buffer(self.h, which)
-        if not ptr:
-            raise RuntimeError(f"lle_coop_buffer failed: {lib().lle_coop_last_error().decode()}")
-
-        class _Array:  # (the array interface keeps no owner: the handle owns the memory)
-            __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
-        return torch.as_tensor(_Array(), device=self.world.device)
+        return _binding.tracker_view(lib(), "lle_coop", self.h, which, shape, typestr, self.world.device)
 
     def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError(f"liblle_coop call failed ({rc}): {lib().lle_coop_last_error().decode()}")
+        _binding.tracker_check(lib(), "lle_coop", rc)
 
     # ------------------------------------------------------------------ updates
     def make_args(self, ops, honour_auto_reset=False, env_mask=None, env_sources=None):

@@ -16,7 +16,8 @@ The module is loaded only when such a tracker is asked for.  No fallback: a miss
 import ctypes as C
 import os
 
-from . import cooperation
+from . import _binding, cooperation
+from ._binding import UpdateArgs  # lle_cooptrails_update_args: the layout of lle_coop_update_args
 from .cooperation import CooperationTracker
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -34,11 +35,6 @@ EXPORTS = ["lle_cooptrails_create", "lle_cooptrails_update_map", "lle_cooptrails
            "lle_cooptrails_last_error", "lle_cooptrails_debug_launched", "lle_cooptrails_debug_compiled"]
 
 
-class UpdateArgs(C.Structure):
-    """lle_cooptrails_update_args."""
-    _fields_ = [("struct_bytes", C.c_uint32), ("ops", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32), ("env_mask", C.c_void_p)]
-
-
 _lib = None
 
 
@@ -48,38 +44,21 @@ def lib():
     if _lib is not None:
         return _lib
     cooperation.lib()
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`.  "
-                          "lle_amd has no fallback for the temporal cooperation tracker.")
-    L = C.CDLL(LIB_PATH)
-    vp, i32 = C.c_void_p, C.c_int
-    L.lle_cooptrails_create.restype = vp
-    L.lle_cooptrails_create.argtypes = [vp, vp, vp]
-    L.lle_cooptrails_update_map.restype = i32
-    L.lle_cooptrails_update_map.argtypes = [vp, i32, vp]
-    L.lle_cooptrails_free.restype = None
-    L.lle_cooptrails_free.argtypes = [vp]
-    L.lle_cooptrails_update.restype = i32
-    L.lle_cooptrails_update.argtypes = [vp, C.POINTER(UpdateArgs), vp]
-    L.lle_cooptrails_buffer.restype = vp
-    L.lle_cooptrails_buffer.argtypes = [vp, i32]
-    L.lle_cooptrails_last_error.restype = C.c_char_p
-    L.lle_cooptrails_last_error.argtypes = []
-    for fn in (L.lle_cooptrails_debug_launched, L.lle_cooptrails_debug_compiled):
-        fn.restype = C.c_size_t
-        fn.argtypes = [C.c_char_p, C.c_size_t]
+    L = _binding.load(LIB_PATH, "the temporal cooperation tracker")
+    vp = C.c_void_p
+    _binding.tracker_signatures(L, "lle_cooptrails", [vp, vp, vp], [vp, C.c_int, vp])
     _lib = L
     return L
 
 
 def launched_kernels():
     """Names of the kernels of liblle_cooptrails.so this process has launched (lle_cooptrails_debug_launched)."""
-    return cooperation._names(lib().lle_cooptrails_debug_launched)
+    return _binding.names(lib().lle_cooptrails_debug_launched)
 
 
 def compiled_kernels():
     """Every instantiation the library holds (lle_cooptrails_debug_compiled)."""
-    return cooperation._names(lib().lle_cooptrails_debug_compiled)
+    return _binding.names(lib().lle_cooptrails_debug_compiled)
 
 
 class TemporalCooperationTracker(CooperationTracker):
@@ -103,18 +82,10 @@ class TemporalCooperationTracker(CooperationTracker):
         self.last_tprofile = self._trails_view(LLE_COOPTRAILS_LAST_TPROFILE, (n, 4), "|u1")
 
     def _trails_view(self, which, shape, typestr):
-        import torch
-        ptr = lib().lle_cooptrails_buffer(self.th, which)
-        if not ptr:
-            raise RuntimeError(f"lle_cooptrails_buffer failed: {lib().lle_cooptrails_last_error().decode()}")
-
-        class _Array:  # (the array interface keeps no owner: the handle owns the memory)
-            __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
-        return torch.as_tensor(_Array(), device=self.world.device)
+        return _binding.tracker_view(lib(), "lle_cooptrails", self.th, which, shape, typestr, self.world.device)
 
     def _trails_check(self, rc):
-        if rc != 0:
-            raise RuntimeError(f"liblle_cooptrails call failed ({rc}): {lib().lle_cooptrails_last_error().decode()}")
+        _binding.tracker_check(lib(), "lle_cooptrails", rc)
 
     # ------------------------------------------------------------------ updates
     def make_trails_args(self, ops, honour_auto_reset=False, env_mask=None, skip_refused=False):

@@ -13,22 +13,20 @@
 // stores.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <atomic>
 #include <cstdint>
-#include <cstring>
-#include <string>
-#include <vector>
 
 #include "../../include/lle_cooptrails.h"
+#include "../coop/tracker_core.hpp"
 #include "cooptrails_logic.hpp"
+
+namespace ct = lle_cooptrails_logic;
+namespace eo = lle_episode_ops;
 
 namespace lle {
 
-namespace ct = lle_cooptrails_logic;
-
 constexpr int COOPTRAILS_THREADS = 256;
-constexpr int START_PITCH = 16;  // per map: the start edges of every agent
+using lle_tracker_core::START_PITCH;  // per map: the start edges of every agent
 
 struct CoopTrailsParams {
     const uint32_t* step_edges;  // LLE_COOP_STEP_EDGES [n][A]
@@ -73,11 +71,9 @@ __global__ __launch_bounds__(COOPTRAILS_THREADS) void cooptrails_kernel(CoopTrai
     // lanes of the own group, and none of them sits inside a walk)
     if (env >= p.n_envs) return;
     if (p.env_mask && p.env_mask[env] == 0) return;
-    const bool was_reset = (p.flags & LLE_COOPTRAILS_HONOUR_AUTO_RESET) && (p.evcount[env] & 0x80u);
-    const uint32_t reset_ops = was_reset ? (uint32_t)(LLE_COOPTRAILS_FINISH | LLE_COOPTRAILS_CLEAR | LLE_COOPTRAILS_MARK_STARTS) : 0u;
+    const uint32_t reset_ops = eo::reset_ops(p.flags, p.evcount + env);
     if ((p.ops | reset_ops) == 0u) return;
-    const bool refused = (p.flags & LLE_COOPTRAILS_SKIP_REFUSED) && p.err[env] != 0;
-    const uint32_t own_ops = refused ? p.ops & ~(uint32_t)LLE_COOPTRAILS_MARK_POS : p.ops;
+    const uint32_t own_ops = eo::own_ops(p.ops, p.flags, p.err + env);
     const bool agent = a < p.A;  // lanes A .. G-1 of a group carry no agent: their rows are zero and they walk nothing
 
     // ---- lane a loads row a of both layers; the group gathers every row into every lane
@@ -104,8 +100,8 @@ __global__ __launch_bounds__(COOPTRAILS_THREADS) void cooptrails_kernel(CoopTrai
 
     // ---- the operations: the auto-reset's, then the caller's; stage 2 is the caller's MARK_POS (one walk in the code, not three)
 #pragma unroll 1
-    for (int stage = 0; stage < 3; stage++) {
-        const uint32_t ops = stage == 0 ? reset_ops : stage == 1 ? own_ops & ~(uint32_t)LLE_COOPTRAILS_MARK_POS : own_ops & (uint32_t)LLE_COOPTRAILS_MARK_POS;
+    for (int stage = 0; stage < eo::STAGES; stage++) {
+        const uint32_t ops = eo::stage_ops(reset_ops, own_ops, stage);
         if (ops & LLE_COOPTRAILS_FINISH) {
             last = L;
             last_prof = ct::longest(L) | count << 8 | dense << 16 | valid;
@@ -142,44 +138,25 @@ template __global__ void cooptrails_kernel<16>(CoopTrailsParams);
 
 }  // namespace lle
 
-// ================================================================================================ host side
+// ================================================================================================ host side (../coop/tracker_core.hpp)
 using lle::CoopTrailsParams;
+using namespace lle_abi_host;
+namespace tc = lle_tracker_core;
+
+static_assert(LLE_COOPTRAILS_FINISH == eo::FINISH && LLE_COOPTRAILS_CLEAR == eo::CLEAR && LLE_COOPTRAILS_MARK_STARTS == eo::MARK_STARTS &&
+                  LLE_COOPTRAILS_MARK_POS == eo::MARK_POS && LLE_COOPTRAILS_HONOUR_AUTO_RESET == eo::HONOUR_AUTO_RESET &&
+                  LLE_COOPTRAILS_SKIP_REFUSED == eo::SKIP_REFUSED && LLE_COOPTRAILS_BUF_COUNT == tc::N_ARRAYS,
+              "the shared decode and the shared handle read this header's values");
+
+struct lle_cooptrails : tc::Tracker<CoopTrailsParams> {
+    int log2_g = 0;
+};
 
 namespace {
 
-thread_local std::string g_error;
 std::atomic<uint32_t> g_launched{0};
 // bit log2(G)
 const char* const KERNEL_NAMES[5] = {"cooptrails_kernel<1>", "cooptrails_kernel<2>", "cooptrails_kernel<4>", "cooptrails_kernel<8>", "cooptrails_kernel<16>"};
-
-int fail(int code, const std::string& why) {
-    g_error = why;
-    return code;
-}
-
-struct DeviceGuard {  // the handle's device current for the call, the caller's put back
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-size_t names_out(uint32_t bits, char* buf, size_t cap) {
-    std::string s;
-    for (int k = 0; k < 5; k++)
-        if ((bits >> k) & 1u) s += std::string(KERNEL_NAMES[k]) + "\n";
-    if (buf && cap > 0) {
-        const size_t n = std::min(cap - 1, s.size());
-        std::memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return s.size() + 1;
-}
 
 // One launch of cooptrails_kernel<1 << log2_g> over p.n_envs environments.
 int launch(const CoopTrailsParams& p, int log2_g, hipStream_t st) {
@@ -203,158 +180,37 @@ int launch(const CoopTrailsParams& p, int log2_g, hipStream_t st) {
 
 }  // namespace
 
-struct lle_cooptrails {
-    int device = 0;
-    int n_maps = 0;
-    int log2_g = 0;
-    const lle_coop* coop = nullptr;
-    uint32_t* d_starts = nullptr;
-    uint8_t* d_state = nullptr;  // the four arrays between guard bytes
-    CoopTrailsParams p{};
-};
-
-namespace {
-
-// The start edges of map `m` from the coop handle to the device (synchronises `st`).
-int upload_starts(lle_cooptrails* t, int m, hipStream_t st) {
-    uint32_t rows[lle::START_PITCH] = {0};
-    const int A = lle_coop_start_edges(t->coop, m, rows, lle::START_PITCH);
-    if (A != t->p.A) return fail(LLE_ERR_ARG, std::string("lle_coop_start_edges: ") + (A < 0 ? lle_coop_last_error() : "another number of agents"));
-    if (hipMemcpyAsync(t->d_starts + (size_t)m * lle::START_PITCH, rows, sizeof(rows), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(LLE_ERR_HIP, "uploading the start edges failed");
-    }
-    return LLE_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 const char* lle_cooptrails_last_error(void) { return g_error.c_str(); }
 
-void lle_cooptrails_free(lle_cooptrails* t) {
-    if (!t) return;
-    DeviceGuard g(t->device);
-    (void)hipFree(t->d_starts);
-    (void)hipFree(t->d_state);
-    delete t;
-}
+void lle_cooptrails_free(lle_cooptrails* t) { tc::destroy(t); }
 
 lle_cooptrails* lle_cooptrails_create(lle_batch* batch, lle_coop* coop, void* stream) {
-    int n_devices = 0;
-    if (hipGetDeviceCount(&n_devices) != hipSuccess || n_devices <= 0) {
-        (void)hipGetLastError();
-        fail(LLE_ERR_NO_DEVICE, "no HIP device: the temporal cooperation tracker runs on the GPU only (there is no CPU fallback)");
-        return nullptr;
-    }
-    if (!batch || !coop) {
-        fail(LLE_ERR_NULL, "NULL batch or coop handle");
-        return nullptr;
-    }
-    lle_buffer_desc evcount{}, err{};
-    if (lle_batch_get_buffer(batch, LLE_BUF_EVCOUNT, &evcount) || lle_batch_get_buffer(batch, LLE_BUF_ERR, &err)) {
-        fail(LLE_ERR_ARG, "lle_batch_get_buffer failed");
-        return nullptr;
-    }
-    void* step_edges = lle_coop_buffer(coop, LLE_COOP_STEP_EDGES);
-    const int A = lle_coop_start_edges(coop, 0, nullptr, 0);
-    const int n_maps = lle_batch_n_maps(batch);
-    const int64_t n = lle_batch_n_envs(batch);
-    if (!step_edges || A < 1 || A > 16 || n_maps <= 0 || n <= 0 || n % n_maps != 0) {
-        fail(LLE_ERR_ARG, "the coop handle or the batch is not usable (agents, maps or environments out of range)");
-        return nullptr;
-    }
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, step_edges) != hipSuccess) {
-        (void)hipGetLastError();
-        fail(LLE_ERR_HIP, "the coop handle's arrays are not device memory");
-        return nullptr;
-    }
-    auto* t = new lle_cooptrails();
-    t->device = attr.device;
-    t->n_maps = n_maps;
-    t->coop = coop;
-    DeviceGuard g(t->device);
-    // the four arrays, each starting on a 256-byte boundary between runs of LLE_COOP_GUARD_BYTES zero bytes that no launch writes
-    const size_t guard = LLE_COOP_GUARD_BYTES;
-    const size_t sizes[LLE_COOPTRAILS_BUF_COUNT] = {(size_t)n * 8, (size_t)n * 8, (size_t)n * 4, (size_t)n * 4};
-    size_t offsets[LLE_COOPTRAILS_BUF_COUNT], state_bytes = guard;
-    for (int k = 0; k < LLE_COOPTRAILS_BUF_COUNT; k++) {
-        offsets[k] = state_bytes;
-        state_bytes += (sizes[k] + guard - 1) / guard * guard + guard;
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const size_t start_bytes = (size_t)n_maps * lle::START_PITCH * 4;
-    if (hipMalloc(&t->d_starts, start_bytes) != hipSuccess || hipMalloc(&t->d_state, state_bytes) != hipSuccess ||
-        hipMemsetAsync(t->d_starts, 0, start_bytes, st) != hipSuccess || hipMemsetAsync(t->d_state, 0, state_bytes, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError();
-        fail(LLE_ERR_HIP, "allocating the cooptrails arrays failed");
-        lle_cooptrails_free(t);
-        return nullptr;
-    }
+    auto* t = tc::bind<lle_cooptrails>(batch, coop, "no HIP device: the temporal cooperation tracker runs on the GPU only (there is no CPU fallback)",
+                                       tc::AgentLimit{ct::MAX_AGENTS, nullptr});
+    if (!t || !tc::allocate(t, {8, 8, 4, 4}, "allocating the cooptrails arrays failed", stream)) return nullptr;
     CoopTrailsParams& p = t->p;
-    p.step_edges = static_cast<const uint32_t*>(step_edges);
-    p.starts = t->d_starts;
-    p.evcount = static_cast<const uint8_t*>(evcount.ptr);
-    p.err = static_cast<const uint8_t*>(err.ptr);
-    p.episode_trails = reinterpret_cast<uint64_t*>(t->d_state + offsets[LLE_COOPTRAILS_EPISODE_TRAILS]);
-    p.last_trails = reinterpret_cast<uint64_t*>(t->d_state + offsets[LLE_COOPTRAILS_LAST_TRAILS]);
-    p.episode_tprofile = reinterpret_cast<uint32_t*>(t->d_state + offsets[LLE_COOPTRAILS_EPISODE_TPROFILE]);
-    p.last_tprofile = reinterpret_cast<uint32_t*>(t->d_state + offsets[LLE_COOPTRAILS_LAST_TPROFILE]);
-    p.n_envs = n;
-    p.envs_per_map = n / n_maps;
-    p.A = A;
+    p.episode_trails = reinterpret_cast<uint64_t*>(t->arrays[LLE_COOPTRAILS_EPISODE_TRAILS]);
+    p.last_trails = reinterpret_cast<uint64_t*>(t->arrays[LLE_COOPTRAILS_LAST_TRAILS]);
+    p.episode_tprofile = reinterpret_cast<uint32_t*>(t->arrays[LLE_COOPTRAILS_EPISODE_TPROFILE]);
+    p.last_tprofile = reinterpret_cast<uint32_t*>(t->arrays[LLE_COOPTRAILS_LAST_TPROFILE]);
     int G = 1;
-    while (G < A) G <<= 1, t->log2_g++;
-    for (int m = 0; m < n_maps; m++) {
-        if (upload_starts(t, m, st) != LLE_OK) {
-            lle_cooptrails_free(t);
-            return nullptr;
-        }
-    }
-    g_error.clear();
+    while (G < p.A) G <<= 1, t->log2_g++;
     return t;
 }
 
-int lle_cooptrails_update_map(lle_cooptrails* t, int map_index, void* stream) {
-    if (!t) return fail(LLE_ERR_NULL, "NULL handle");
-    if (map_index < 0 || map_index >= t->n_maps) return fail(LLE_ERR_ARG, "map_index out of range");
-    DeviceGuard g(t->device);
-    return upload_starts(t, map_index, reinterpret_cast<hipStream_t>(stream));
-}
+int lle_cooptrails_update_map(lle_cooptrails* t, int map_index, void* stream) { return tc::update_map(t, map_index, stream); }
 
 void* lle_cooptrails_buffer(lle_cooptrails* t, int which) {
-    if (!t || which < 0 || which >= LLE_COOPTRAILS_BUF_COUNT) {
-        fail(LLE_ERR_ARG, "NULL handle or `which` not one of LLE_COOPTRAILS_EPISODE_TRAILS ... LLE_COOPTRAILS_LAST_TPROFILE");
-        return nullptr;
-    }
-    switch (which) {
-        case LLE_COOPTRAILS_EPISODE_TRAILS: return t->p.episode_trails;
-        case LLE_COOPTRAILS_LAST_TRAILS: return t->p.last_trails;
-        case LLE_COOPTRAILS_EPISODE_TPROFILE: return t->p.episode_tprofile;
-        default: return t->p.last_tprofile;
-    }
+    return tc::buffer(t, which, "NULL handle or `which` not one of LLE_COOPTRAILS_EPISODE_TRAILS ... LLE_COOPTRAILS_LAST_TPROFILE");
 }
 
 int lle_cooptrails_update(lle_cooptrails* t, const lle_cooptrails_update_args* args, void* stream) {
-    if (!t || !args) return fail(LLE_ERR_NULL, "NULL handle or arguments");
-    if (args->struct_bytes != sizeof(lle_cooptrails_update_args))
-        return fail(LLE_ERR_ARG, "lle_cooptrails_update_args.struct_bytes is not sizeof(lle_cooptrails_update_args)");
-    const uint32_t all_ops = LLE_COOPTRAILS_FINISH | LLE_COOPTRAILS_CLEAR | LLE_COOPTRAILS_MARK_STARTS | LLE_COOPTRAILS_MARK_POS;
-    const uint32_t all_flags = LLE_COOPTRAILS_HONOUR_AUTO_RESET | LLE_COOPTRAILS_SKIP_REFUSED;
-    if ((args->ops & ~all_ops) || (args->flags & ~all_flags)) return fail(LLE_ERR_ARG, "unknown operation or flag");
-    CoopTrailsParams p = t->p;
-    p.ops = args->ops;
-    p.flags = args->flags;
-    p.env_mask = args->env_mask;
-    DeviceGuard g(t->device);
-    return launch(p, t->log2_g, reinterpret_cast<hipStream_t>(stream));
+    return tc::update(t, args, "lle_cooptrails_update_args", stream, [t](const CoopTrailsParams& p, hipStream_t st) { return launch(p, t->log2_g, st); });
 }
 
-size_t lle_cooptrails_debug_launched(char* buf, size_t cap) { return names_out(g_launched.load(), buf, cap); }
-size_t lle_cooptrails_debug_compiled(char* buf, size_t cap) { return names_out(0x1Fu, buf, cap); }
+size_t lle_cooptrails_debug_launched(char* buf, size_t cap) { return names_out(KERNEL_NAMES, 5, g_launched.load(), buf, cap); }
+size_t lle_cooptrails_debug_compiled(char* buf, size_t cap) { return names_out(KERNEL_NAMES, 5, 0x1Fu, buf, cap); }
 
 }  // extern "C"

@@ -13,6 +13,8 @@
 
 #include <stdint.h>
 
+#include "../coop/episode_ops.hpp"
+
 #if defined(__HIPCC__)
 #define LLE_COOPTRAILS_HD __host__ __device__ inline
 #else
@@ -45,8 +47,7 @@ LLE_COOPTRAILS_HD Arcs with_bits(Arcs e, int h, uint32_t bits, bool on) {
     else { e.w0 &= ~m0; e.w1 &= ~m1; e.w2 &= ~m2; e.w3 &= ~m3; }
     return e;
 }
-// Row h of a state as the coop kernel stores it (a u32 of LLE_COOP_STEP_EDGES): bits of agents >= A and the self-loop dropped.
-LLE_COOPTRAILS_HD uint32_t clean_row(uint32_t row, int h, int A) { return row & ((1u << A) - 1u) & ~(1u << h) & 0xFFFFu; }
+using lle_episode_ops::clean_row;  // a row of LLE_COOP_STEP_EDGES without the bits of agents >= A and without the self-loop
 
 LLE_COOPTRAILS_HD uint32_t field(uint64_t L, int a) { return (uint32_t)(L >> (4 * a)) & 15u; }
 LLE_COOPTRAILS_HD uint64_t with_field(uint64_t L, int a, uint32_t v) { return (L & ~((uint64_t)15 << (4 * a))) | (uint64_t)v << (4 * a); }

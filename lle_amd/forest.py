@@ -18,7 +18,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import _capi
+from . import _binding, _capi
 from .solver import (LLE_SEARCH_CAPACITY, LLE_SEARCH_MAX_AGENTS, _NATIVE, SearchArgs, SolverCapacityError, _as_world, _device_index, _native_mode)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -74,21 +74,14 @@ def lib():
     return L
 
 
-def _names(fn):
-    need = fn(None, 0)
-    buf = C.create_string_buffer(need)
-    fn(buf, need)
-    return [n for n in buf.value.decode().split("\n") if n]
-
-
 def launched_kernels():
     """Names of the kernels of liblle_forest.so this process has launched (lle_forest_debug_launched)."""
-    return _names(lib().lle_forest_debug_launched)
+    return _binding.names(lib().lle_forest_debug_launched)
 
 
 def compiled_kernels():
     """Every kernel the library holds (lle_forest_debug_compiled)."""
-    return _names(lib().lle_forest_debug_compiled)
+    return _binding.names(lib().lle_forest_debug_compiled)
 
 
 # ------------------------------------------------------------------------------------------------ shapes

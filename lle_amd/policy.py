@@ -19,7 +19,7 @@ The module is loaded only when a policy is asked for.  No fallback: a missing li
 import ctypes as C
 import os
 
-from . import _capi
+from . import _binding, _capi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblle_policy.so")
@@ -85,21 +85,14 @@ def lib():
     return L
 
 
-def _names(fn):
-    need = fn(None, 0)
-    buf = C.create_string_buffer(need)
-    fn(buf, need)
-    return [n for n in buf.value.decode().split("\n") if n]
-
-
 def launched_kernels():
     """Names of the kernels of liblle_policy.so this process has launched (lle_policy_debug_launched)."""
-    return _names(lib().lle_policy_debug_launched)
+    return _binding.names(lib().lle_policy_debug_launched)
 
 
 def compiled_kernels():
     """Every kernel the library holds (lle_policy_debug_compiled)."""
-    return _names(lib().lle_policy_debug_compiled)
+    return _binding.names(lib().lle_policy_debug_compiled)
 
 
 def map_fingerprint(map_):

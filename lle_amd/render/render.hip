@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/lle_render.h"
+#include "../common/abi_host.hpp"
 
 // Rust does not contract `(1 - a) * bg + a * fg` into an FMA; clang would (host and device): every blend below is
 // rounded op by op.
@@ -233,17 +234,12 @@ template __global__ void render_kernel<3>(RenderParams);
 
 // ================================================================================================ host side
 using lle::RenderParams;
+using namespace lle_abi_host;
 
 namespace {
 
-thread_local std::string g_error;
 std::atomic<uint32_t> g_launched{0};
 const char* const KERNEL_NAMES[4] = {"render_kernel<0>", "render_kernel<1>", "render_kernel<2>", "render_kernel<3>"};
-
-int fail(int code, const std::string& why) {
-    g_error = why;
-    return code;
-}
 
 struct MapStatics {
     int32_t H = 0, W = 0, A = 0, n_sources = 0;
@@ -351,18 +347,6 @@ struct lle_renderer {
 };
 
 namespace {
-
-struct DeviceGuard {  // the renderer's device current for the call, the caller's put back
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
 
 int upload_tables(lle_renderer* r, hipStream_t st) {
     std::vector<uint32_t> all;
@@ -592,17 +576,6 @@ int lle_render_frame(lle_renderer* r, const int64_t* env_ids_dev, int64_t n_sel,
     return LLE_OK;
 }
 
-size_t lle_render_debug_launched(char* buf, size_t cap) {
-    std::string s;
-    const uint32_t bits = g_launched.load();
-    for (int k = 0; k < 4; k++)
-        if ((bits >> k) & 1u) s += std::string(KERNEL_NAMES[k]) + "\n";
-    if (buf && cap > 0) {
-        const size_t n = std::min(cap - 1, s.size());
-        std::memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return s.size() + 1;
-}
+size_t lle_render_debug_launched(char* buf, size_t cap) { return names_out(KERNEL_NAMES, 4, g_launched.load(), buf, cap); }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/lle_hip.h"
+#include "../common/abi_host.hpp"
 #include "search_logic.hpp"
 
 namespace lle_search_device {
@@ -23,37 +24,11 @@ namespace {
 
 namespace sl = lle_search_logic;
 
-thread_local std::string g_error;
-
-int fail(int code, const std::string& why) {
-    g_error = why;
-    return code;
-}
-
-struct DeviceGuard {  // the handle's device current for the call, the caller's put back
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-// The names whose bit is set, one per line, into buf (truncated to cap); returns the bytes the whole text needs.
-size_t names_out(const char* const* names, int count, uint32_t bits, char* buf, size_t cap) {
-    std::string s;
-    for (int k = 0; k < count; k++)
-        if ((bits >> k) & 1u) s += std::string(names[k]) + "\n";
-    if (buf && cap > 0) {
-        const size_t n = std::min(cap - 1, s.size());
-        std::memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return s.size() + 1;
-}
+// the error string, fail, the device guard and names_out of ../common/abi_host.hpp, under this namespace's names
+using lle_abi_host::DeviceGuard;
+using lle_abi_host::fail;
+using lle_abi_host::g_error;
+using lle_abi_host::names_out;
 
 // opt_device, or the current device when it is negative.  `no_device` is the library's text for a machine without one.
 int choose_device(int opt_device, const char* no_device, int* device) {

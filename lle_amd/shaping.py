@@ -12,7 +12,7 @@ namespace package, and a package of that name would shadow the binding (the rend
 import ctypes as C
 import os
 
-from . import _capi
+from . import _binding, _capi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblle_shaping.so")
@@ -74,21 +74,14 @@ def lib():
     return L
 
 
-def _names(fn):
-    need = fn(None, 0)
-    buf = C.create_string_buffer(need)
-    fn(buf, need)
-    return [n for n in buf.value.decode().split("\n") if n]
-
-
 def launched_kernels():
     """Names of the kernels of liblle_shaping.so this process has launched (lle_shaping_debug_launched)."""
-    return _names(lib().lle_shaping_debug_launched)
+    return _binding.names(lib().lle_shaping_debug_launched)
 
 
 def compiled_kernels():
     """Every instantiation the library holds (lle_shaping_debug_compiled)."""
-    return _names(lib().lle_shaping_debug_compiled)
+    return _binding.names(lib().lle_shaping_debug_compiled)
 
 
 def cell_masks(map_):

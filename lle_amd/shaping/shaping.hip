@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/lle_shaping.h"
+#include "../common/abi_host.hpp"
 
 // `gamma * prev - cur` must round the product before the subtraction, like numpy on Python floats: no FMA (also -ffp-contract=off).
 #pragma clang fp contract(off)
@@ -155,20 +156,15 @@ LLE_SHAPING_INSTANTIATE(16)
 
 // ================================================================================================ host side
 using lle::ShapingParams;
+using namespace lle_abi_host;
 
 namespace {
 
-thread_local std::string g_error;
 std::atomic<uint32_t> g_launched{0};
 // bit 2 * log2(G) + LDS_TABLE
 const char* const KERNEL_NAMES[10] = {"shaping_kernel<1,false>", "shaping_kernel<1,true>",  "shaping_kernel<2,false>",  "shaping_kernel<2,true>",
                                       "shaping_kernel<4,false>", "shaping_kernel<4,true>",  "shaping_kernel<8,false>",  "shaping_kernel<8,true>",
                                       "shaping_kernel<16,false>", "shaping_kernel<16,true>"};
-
-int fail(int code, const std::string& why) {
-    g_error = why;
-    return code;
-}
 
 struct MapTables {
     int32_t H = 0, W = 0, A = 0, n_sources = 0;
@@ -200,30 +196,6 @@ bool build_map(const lle_map* map, MapTables& mt, std::string& err) {
         mt.starts[(size_t)a] = mt.cells[(size_t)i * mt.W + j];
     }
     return true;
-}
-
-struct DeviceGuard {  // the handle's device current for the call, the caller's put back
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-size_t names_out(uint32_t bits, char* buf, size_t cap) {
-    std::string s;
-    for (int k = 0; k < 10; k++)
-        if ((bits >> k) & 1u) s += std::string(KERNEL_NAMES[k]) + "\n";
-    if (buf && cap > 0) {
-        const size_t n = std::min(cap - 1, s.size());
-        std::memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return s.size() + 1;
 }
 
 }  // namespace
@@ -475,7 +447,7 @@ int lle_shaping_update(lle_shaping* s, const lle_shaping_update_args* args, void
     return LLE_OK;
 }
 
-size_t lle_shaping_debug_launched(char* buf, size_t cap) { return names_out(g_launched.load(), buf, cap); }
-size_t lle_shaping_debug_compiled(char* buf, size_t cap) { return names_out(0x3FFu, buf, cap); }
+size_t lle_shaping_debug_launched(char* buf, size_t cap) { return names_out(KERNEL_NAMES, 10, g_launched.load(), buf, cap); }
+size_t lle_shaping_debug_compiled(char* buf, size_t cap) { return names_out(KERNEL_NAMES, 10, 0x3FFu, buf, cap); }
 
 }  // extern "C"

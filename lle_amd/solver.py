@@ -20,7 +20,7 @@ import ctypes as C
 import os
 import re
 
-from . import _capi
+from . import _binding, _capi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblle_search.so")
@@ -85,11 +85,7 @@ def lib():
     return L
 
 
-def _names(fn):
-    need = fn(None, 0)
-    buf = C.create_string_buffer(need)
-    fn(buf, need)
-    return [n for n in buf.value.decode().split("\n") if n]
+_names = _binding.names
 
 
 def launched_kernels():

@@ -14,7 +14,7 @@ import pytest
 from lle_amd import Map, cooperation
 from lle_amd.characterization import DependencyEdge, PlanProfile, TemporalCooperationGraph
 from oracle.levels import LEVELS
-from tests import coop_ref
+from tests import coop_ref, coopcycles_ref, cooptrails_ref, source_text
 from tests.oracle_shaping import SHAPING_MAPS
 from tests.parity_util import EXTRA_MAPS, LONG_MAPS
 
@@ -119,7 +119,7 @@ def test_library_exports():
     declared = set(re.findall(r"\b(lle_coop_[a-z_0-9]+)\s*\(", header))
     assert declared == set(cooperation.EXPORTS)
     assert all(hasattr(L, s) for s in declared)
-    assert '#include "../../include/lle_coop.h"' in open(os.path.join(ROOT, "lle_amd", "coop", "coop.hip")).read()
+    assert '#include "../../include/lle_coop.h"' in source_text.text_of(os.path.join("lle_amd", "coop", "coop.hip"))
     prog = ('#include <stdio.h>\n#include "lle_coop.h"\nint main(void) { printf("%zu %d %d %d %d %d %d %d %d %d", sizeof(lle_coop_update_args), '
             'LLE_COOP_FINISH, LLE_COOP_CLEAR, LLE_COOP_MARK_STARTS, LLE_COOP_MARK_POS, LLE_COOP_HONOUR_AUTO_RESET, LLE_COOP_ENV_SOURCES, '
             'LLE_COOP_EPISODE_EDGES, LLE_COOP_LAST_PROFILE, LLE_COOP_BUF_COUNT); return 0; }\n')
@@ -133,6 +133,53 @@ def test_library_exports():
                    cooperation.LLE_COOP_EPISODE_EDGES, cooperation.LLE_COOP_LAST_PROFILE, 5]
     assert sorted(cooperation.compiled_kernels()) == sorted(f"coop_kernel<{g},{t}>" for g in (1, 2, 4, 8, 16) for t in ("false", "true"))
     assert cooperation.launched_kernels() == []
+
+
+def test_episode_ops_under_sanitizers(tmp_path):
+    """tests/hostsim/episode_ops.cpp: its own main over lle_amd/coop/episode_ops.hpp, built with g++ -fsanitize=address,undefined and
+    run as a child process; nothing sanitized is loaded into this interpreter.  Every decode case goes to it as text: 16 operation
+    words x HONOUR_AUTO_RESET x SKIP_REFUSED x bit 7 of the event count x the error byte, 256 in all, with the operations of stages
+    0, 1 and 2 by the order EnvRef.update of tests/cooptrails_ref.py and tests/coopcycles_ref.py implements: the auto-reset's phase,
+    then the caller's, MARK_POS last inside a phase.  The layout function is judged on what the program prints: the properties
+    include/lle_coop.h promises for a handle's arrays."""
+    FINISH, CLEAR, MARK_STARTS, MARK_POS = cooptrails_ref.FINISH, cooptrails_ref.CLEAR, cooptrails_ref.MARK_STARTS, cooptrails_ref.MARK_POS
+    assert (FINISH, CLEAR, MARK_STARTS, MARK_POS) == (coopcycles_ref.FINISH, coopcycles_ref.CLEAR, coopcycles_ref.MARK_STARTS, coopcycles_ref.MARK_POS)
+    exe, cases = str(tmp_path / "episode_ops"), str(tmp_path / "cases.txt")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(ROOT, "tests", "hostsim", "episode_ops.cpp"), "-o", exe,
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"], check=True)
+    layouts = [[1], [255], [256], [257], [1, 255, 256, 257], [4096 * 8, 4096 * 8, 4096 * 4, 4096 * 4], [7 * 4 * 21, 7 * 4 * 21, 28, 28]]
+    n_cases = unread = 0
+    with open(cases, "w") as f:
+        for ops in range(16):
+            for honour in (0, 1):
+                for skip in (0, 2):
+                    for evcount in (0x7F, 0x85):
+                        for err in (0, 3):
+                            was_reset, refused = bool(honour and evcount & 0x80), bool(skip and err)
+                            phases = ([FINISH | CLEAR | MARK_STARTS] if was_reset else []) + [ops & ~MARK_POS if refused else ops]  # EnvRef.update
+                            stages = [phases[0] if was_reset else 0, phases[-1] & ~MARK_POS, phases[-1] & MARK_POS]
+                            for ref in (cooptrails_ref.EnvRef(2), coopcycles_ref.EnvRef(2)):  # what the restatements make of the same call
+                                ref.update(ops, was_reset=was_reset, refused=refused)
+                                assert ref.touched == bool(ops or was_reset) and (not ref.touched or ref.finished == any(s & FINISH for s in stages))
+                            f.write("ops " + " ".join(format(v, "x") for v in [ops, honour | skip, evcount, err] + stages) + "\n")
+                            n_cases, unread = n_cases + 1, unread + (not honour) + (not skip)
+        for sizes in layouts:
+            f.write(f"layout {len(sizes)} " + " ".join(str(s) for s in sizes) + "\n")
+    assert n_cases == 256
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    res = subprocess.run([exe, cases], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=120)
+    assert res.returncode == 0, f"rc={res.returncode}\n{res.stdout[-3000:]}\n{res.stderr[-6000:]}"
+    lines = res.stdout.splitlines()
+    assert lines[-1] == f"OK decoded=256 layouts={len(layouts)} unread={unread}" and len(lines) == len(layouts) + 1
+    guard = 256  # LLE_COOP_GUARD_BYTES
+    for sizes, line in zip(layouts, lines):
+        got = [int(v) for v in line.split()[1:]]
+        k, offsets, total = got[0], got[1:-1], got[-1]
+        assert k == len(sizes) == len(offsets)
+        assert all(o % guard == 0 for o in offsets) and offsets[0] >= guard                     # every array on a 256-byte boundary, a guard in front
+        assert all(offsets[i + 1] - (offsets[i] + sizes[i]) >= guard for i in range(k - 1))    # a guard between an array's end and the next one's start
+        assert total - (offsets[-1] + sizes[-1]) >= guard and total % guard == 0                # a guard behind the last
+        assert total <= sum(sizes) + (2 * k + 1) * guard                                        # and no more than rounding plus the guards
 
 
 def test_host_side_refusals():

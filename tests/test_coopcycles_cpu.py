@@ -17,7 +17,7 @@ import pytest
 import lle_amd
 from lle_amd import coopcycles, cycles
 from lle_amd.characterization import DependencyEdge, TemporalCooperationGraph
-from tests import coopcycles_play, coopcycles_ref, cycles_ref
+from tests import coopcycles_play, coopcycles_ref, cycles_ref, source_text
 from tests.coopcycles_ref import CLEAR, FINISH, MARK_POS, MARK_STARTS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -140,10 +140,13 @@ def test_values_under_sanitizers(tmp_path):
 
 
 def test_source_is_plain_code_over_the_public_abi():
-    source = open(os.path.join(ROOT, "lle_amd", "coopcycles", "coopcycles.hip")).read()
+    hip = os.path.join("lle_amd", "coopcycles", "coopcycles.hip")
+    source = source_text.text_of(hip)  # the .hip and the headers of lle_amd/ it includes
+    assert {os.path.basename(p) for p in source_text.files_of(hip)} == {"coopcycles.hip", "cycles_logic.hpp", "helpgraph_logic.hpp", "search_logic.hpp",
+                                                                        "tracker_core.hpp", "episode_ops.hpp", "abi_host.hpp"}
     assert not re.search(r"\b(__)?asm(__)?\b", source)  # plain C++ only
     assert '#include "../cycles/cycles_logic.hpp"' in source and "cl::layer_update<W>" in source and "cl::Order{A, ~0ull, 0ull}" in source
-    assert "getenv" not in source and "hipMalloc" not in source[source.index("int lle_coopcycles_update("):]
+    assert "getenv" not in source and "hipMalloc" not in source_text.update_path_of(hip, "int lle_coopcycles_update(")
     # over the public ABI only: the batch through lle_batch_get_buffer, the coop handle through its buffer and start edges
     used = set(re.findall(r"\b(lle_(?:batch|coop|map|cooptrails|cycles)_[a-z_0-9]+)\s*\(", source))
     assert used == {"lle_batch_get_buffer", "lle_batch_n_envs", "lle_batch_n_maps", "lle_coop_buffer", "lle_coop_start_edges", "lle_coop_last_error"}
@@ -158,7 +161,7 @@ def test_library_exports():
     declared = set(re.findall(r"\b(lle_coopcycles_[a-z_0-9]+)\s*\(", header))
     assert declared == set(coopcycles.EXPORTS)
     assert all(hasattr(L, s) for s in declared)
-    source = open(os.path.join(ROOT, "lle_amd", "coopcycles", "coopcycles.hip")).read()
+    source = source_text.text_of(os.path.join("lle_amd", "coopcycles", "coopcycles.hip"))
     assert '#include "../../include/lle_coopcycles.h"' in source
     names = ["LLE_COOPCYCLES_FINISH", "LLE_COOPCYCLES_CLEAR", "LLE_COOPCYCLES_MARK_STARTS", "LLE_COOPCYCLES_MARK_POS", "LLE_COOPCYCLES_HONOUR_AUTO_RESET",
              "LLE_COOPCYCLES_SKIP_REFUSED", "LLE_COOPCYCLES_EPISODE_CLOSED", "LLE_COOPCYCLES_LAST_CLOSED", "LLE_COOPCYCLES_EPISODE_CPROFILE",

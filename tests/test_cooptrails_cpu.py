@@ -16,7 +16,7 @@ import pytest
 import lle_amd
 from lle_amd import cooptrails
 from lle_amd.characterization import DependencyEdge, TemporalCooperationGraph
-from tests import cooptrails_ref
+from tests import cooptrails_ref, source_text
 from tests.cooptrails_ref import CLEAR, FINISH, MARK_POS, MARK_STARTS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,10 +53,13 @@ def test_logic_header_under_sanitizers(tmp_path):
 
 def test_logic_header_is_plain_code():
     logic = open(os.path.join(ROOT, "lle_amd", "cooptrails", "cooptrails_logic.hpp")).read()
-    source = open(os.path.join(ROOT, "lle_amd", "cooptrails", "cooptrails.hip")).read()
-    assert not re.search(r"\b(__)?asm(__)?\b", source + logic)  # plain C++ only
+    hip = os.path.join("lle_amd", "cooptrails", "cooptrails.hip")
+    source = source_text.text_of(hip)  # the .hip and the headers of lle_amd/ it includes, the logic header among them
+    assert {os.path.basename(p) for p in source_text.files_of(hip)} == {"cooptrails.hip", "cooptrails_logic.hpp", "tracker_core.hpp", "episode_ops.hpp", "abi_host.hpp"}
+    assert not re.search(r"\b(__)?asm(__)?\b", source)  # plain C++ only
     assert "[" not in re.sub(r"//.*", "", logic), "no array in the logic header: nothing is indexed at run time"
-    assert "WALK_BUDGET = 4096" in logic and "getenv" not in source and "hipMalloc" not in source[source.index("int lle_cooptrails_update("):]
+    assert "WALK_BUDGET = 4096" in logic and "getenv" not in source
+    assert "hipMalloc" not in source_text.update_path_of(hip, "int lle_cooptrails_update(")  # no allocation on the update path
     # over the public ABI only: the batch through lle_batch_get_buffer, the coop handle through its buffer and start edges
     used = set(re.findall(r"\b(lle_(?:batch|coop|map)_[a-z_0-9]+)\s*\(", source))
     assert used == {"lle_batch_get_buffer", "lle_batch_n_envs", "lle_batch_n_maps", "lle_coop_buffer", "lle_coop_start_edges", "lle_coop_last_error"}
@@ -141,7 +144,7 @@ def test_library_exports():
     declared = set(re.findall(r"\b(lle_cooptrails_[a-z_0-9]+)\s*\(", header))
     assert declared == set(cooptrails.EXPORTS)
     assert all(hasattr(L, s) for s in declared)
-    source = open(os.path.join(ROOT, "lle_amd", "cooptrails", "cooptrails.hip")).read()
+    source = source_text.text_of(os.path.join("lle_amd", "cooptrails", "cooptrails.hip"))
     assert '#include "../../include/lle_cooptrails.h"' in source and '#include "cooptrails_logic.hpp"' in source
     names = ["LLE_COOPTRAILS_FINISH", "LLE_COOPTRAILS_CLEAR", "LLE_COOPTRAILS_MARK_STARTS", "LLE_COOPTRAILS_MARK_POS", "LLE_COOPTRAILS_HONOUR_AUTO_RESET",
              "LLE_COOPTRAILS_SKIP_REFUSED", "LLE_COOPTRAILS_EPISODE_TRAILS", "LLE_COOPTRAILS_LAST_TRAILS", "LLE_COOPTRAILS_EPISODE_TPROFILE",
