@@ -114,7 +114,9 @@ int lle_policy_stats(const lle_policy* p, int64_t* frontier, int64_t* expanded, 
  * buffers are only read.  The batch's strides are queried once per (policy, batch) pair and kept; at every call the kept entry is
  * checked against the batch's LLE_BUF_POS and LLE_BUF_BEAMS descriptors (a freed batch's address may serve a new one).
  * Refused: no table (never built, or LLE_POLICY_CAPACITY), a batch of several maps, another agent count or beam-word count,
- * another device.  The MAP itself is not compared here: compare lle_policy_map_fingerprint of the two maps. */
+ * another device.  The MAP itself is not compared here: compare lle_policy_map_fingerprint of the two maps.
+ * A batch of several maps (lle_batch_create_multi) is served by liblle_policyforest.so (include/lle_policyforest.h): one table per
+ * map, built in the same launches, and one lookup launch over the whole batch. */
 int lle_policy_lookup(lle_policy* p, const lle_batch* batch, int32_t* steps_out, uint8_t* actions_out, int64_t action_stride, void* stream);
 
 /* Host only (no device needed): a 64-bit hash of what the public lle_map_* queries say about the map's dynamics -- dimensions and

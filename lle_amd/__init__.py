@@ -36,6 +36,9 @@ def __getattr__(name):
     if name in ("OptimalPolicy", "PolicyCapacityError"):  # (steps-to-go and expert actions of a whole batch, liblle_policy.so)
         from . import policy
         return getattr(policy, name)
+    if name == "PolicyForest":  # (one steps-to-go table per map of a multi-map batch, one lookup launch, liblle_policyforest.so)
+        from .policyforest import PolicyForest
+        return PolicyForest
     if name in ("HelpGraphSolver", "HelpGraphCharacterizer"):  # (the solve modes over the help graph, liblle_helpgraph.so)
         from . import helpgraph
         return getattr(helpgraph, name)
@@ -75,4 +78,4 @@ __all__ = ["Action", "Agent", "AgentZeroPerspective", "BatchedLLE", "BatchedWorl
            "OptimalPolicy", "PolicyCapacityError", "HelpGraphSolver", "HelpGraphCharacterizer", "TrailSolver", "TrailCharacterizer",
            "HelpForestSolver", "HelpForestResult", "ManyHelpCharacterization", "TemporalCooperationTracker",
            "CycleSolver", "CycleCharacterizer", "CycleForestSolver", "CycleForestResult", "ManyCycleCharacterization",
-           "ClosedTrailCooperationTracker"]
+           "ClosedTrailCooperationTracker", "PolicyForest"]
