@@ -500,6 +500,17 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
     // ---- n_steps consecutive steps of the wave's environments; the state stays in registers in between.
     // (n_steps = 1 is World.step; more is a fused rollout with on-device action sampling, lle_batch_rollout.)
     StepCounts cnt = {0, 0, 0, 0, 0, 0, 0};
+    // Single steps: the seven counters of the lane's environment as two words of 8-bit fields (step_logic.hpp stat_pack_*), summed over
+    // the wavefront as they are.  No field of the sums carries: a wavefront has 64 / G lead lanes, one step each, and per environment
+    // steps, invalid, resets and bonus are 0 or 1, and gems, exits and deaths are at most A <= G (an agent moves once per step: it collects,
+    // arrives or dies at most once) -- 64 per field; the event list they are counted from cannot hold more than 2 G events whatever
+    // happens, which bounds a field by 128.
+    static_assert(stat_fields_fit(64u / G, G) && stat_fields_fit(64u / G, 2u * G), "the packed counters of a wavefront's single step must fit 8-bit fields");
+    uint32_t cnt_reward = 0u, cnt_flags = 0u;
+    // Single steps write their final state and their counters in post_step (below), wherever that runs.  Not MODE 7 with the beam masks in LDS
+    // (LM = 8): `<4,8,7,*>` sits at 127 vector registers with that code in front of the stream and spills two of them to scratch (113 and no
+    // scratch with it behind the stream), so those instantiations keep both behind the stream.
+    constexpr bool TAIL_IN_POST = !ROLL && !(MODE == 7 && BM);
     // Fused rollouts: the seven per-env counters of the launch live in the wavefront's spare record slots (LDS) instead of seven vector
     // registers carried across the steps -- `ds_add_u32` without a return per step, read back once behind the loop.  The per-env-sources
     // rollout (MODE 3) sits at the register cap.
@@ -509,6 +520,27 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
 #pragma unroll
         for (int q = 0; q < 7; q++) cnt_lds[q] = 0u;
     }
+    // ---- final state.  Written unconditionally: an env whose action was refused kept its registers unchanged
+    // (world.rs:436-453: errors precede any mutation), so this rewrites the same bytes.  Stores only (BM: the masks come from the
+    // env's LDS record).  Single steps: the tail of post_step; a fused rollout: once, behind its steps.
+    auto final_state = [&](int64_t env_f) {
+        if (me) {
+            small_store(LLE_LATE(pos, env_f * As + a), (uint16_t)pos);
+            small_store(LLE_LATE(avail, env_f * As + a), (uint8_t)avail);
+        }
+        if (env_ok && a == 0) {
+            small_store(LLE_LATE(bits, env_f), (uint64_t)alive | ((uint64_t)arrived << 16) | ((uint64_t)occ << 32) | ((uint64_t)ghost << GHOST_SHIFT));
+            small_store(LLE_LATE(gems, env_f), gems);
+            uint32_t* const beams_out = LLE_LATE(beams, env_f * L);
+#pragma unroll
+            for (int b = 0; b < LR; b++)
+                if (!BM && b < L) small_store(&beams_out[b], beams[b]);
+        }
+        if (BM && env_ok) {
+            uint32_t* const beams_out = LLE_LATE(beams, env_f * L);
+            for (int b = (int)a; b < L; b += G) small_store(&beams_out[b], bm[b]);
+        }
+    };
     const uint32_t n_steps = ROLL ? (K.n_steps ? K.n_steps : 1u) : 1u;
     for (uint32_t it = 0; it < n_steps; it++) {
     const uint64_t t_now = K.t + it;
@@ -657,11 +689,15 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
         }
         const uint32_t n_exit = n_ev - n_died - n_gem;
         const uint32_t bonus = (err == 0 && arrived == amask) ? 1u : 0u;
-        small_store(&reward_out[env], n_gem | (n_exit << 8) | (n_died << 16) | (bonus << 24));
+        const uint32_t reward_word = stat_pack_reward(n_gem, n_exit, n_died, bonus);
+        small_store(&reward_out[env], reward_word);
         if (CNT_LDS) {
             const uint32_t add[7] = {1u, n_gem, n_exit, n_died, err != 0 ? 1u : 0u, was_reset, bonus};
 #pragma unroll
             for (int q = 0; q < 7; q++) __hip_atomic_fetch_add(&cnt_lds[q], add[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        } else if (!ROLL) {
+            cnt_reward = reward_word;
+            cnt_flags = stat_pack_flags(1u, err != 0 ? 1u : 0u, was_reset);
         } else {
             cnt.steps += 1u; cnt.gems += n_gem; cnt.exits += n_exit; cnt.died += n_died;
             cnt.invalid += err != 0 ? 1u : 0u; cnt.resets += was_reset; cnt.bonus += bonus;
@@ -760,6 +796,15 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
             }
         }
     }
+    // ---- single steps: the final state and the wavefront's counters belong to this block -- neither depends on the rows -- so a
+    // wavefront that runs it in front of its stream has nothing behind its last row store but the end of the program (the launch ends
+    // with the last wavefront's last acknowledged store).  Stores only: the counters' old values were preloaded (PRE_STATS); where they
+    // are not, the flush reads its slot -- a load in front of the stream would wait for it -- and stays behind the stream (below).
+    // Wave-uniform here, every lane active: `post_first` is uniform.
+    if (TAIL_IN_POST) {
+        final_state(env_p);
+        if (PRE_STATS) flush_stats_packed(P.stats, wave_id_l, cnt_reward, cnt_flags, A, lane, true, stats_old);
+    }
     };  // post_step
 
     if (env_ok && a == 0) {
@@ -856,24 +901,13 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
     }  // steps
     LLE_STAMP(5);
 
-    // ---- final state.  Written unconditionally: an env whose action was refused kept its registers unchanged
-    // (world.rs:436-453: errors precede any mutation), so this rewrites the same bytes.
-    LLE_ENV_LATE(env_f);
-    if (me) {
-        small_store(LLE_LATE(pos, env_f * As + a), (uint16_t)pos);
-        small_store(LLE_LATE(avail, env_f * As + a), (uint8_t)avail);
+    // ---- a fused rollout: the final state and the counters of its steps (32-bit sums: they accumulate over n_steps).  Single steps wrote
+    // both in post_step -- except the counters of the instantiations without PRE_STATS (MODE 4 / 5 / 9, and MODE 0 with 16 / 32 beam
+    // registers), whose flush loads its slot: here, behind the stream.  (!TAIL_IN_POST: everything here, as in a rollout.)
+    if (!TAIL_IN_POST) {
+        LLE_ENV_LATE(env_f);
+        final_state(env_f);
     }
-    if (env_ok && a == 0) {
-        small_store(LLE_LATE(bits, env_f), (uint64_t)alive | ((uint64_t)arrived << 16) | ((uint64_t)occ << 32) | ((uint64_t)ghost << GHOST_SHIFT));
-        small_store(LLE_LATE(gems, env_f), gems);
-        uint32_t* const beams_out = LLE_LATE(beams, env_f * L);
-#pragma unroll
-        for (int b = 0; b < LR; b++)
-            if (!BM && b < L) small_store(&beams_out[b], beams[b]);
-    }
-    if (BM && env_ok) {
-        uint32_t* const beams_out = LLE_LATE(beams, env_f * L);
-        for (int b = (int)a; b < L; b += G) small_store(&beams_out[b], bm[b]);
 #undef LLE_LATE
 #undef LLE_ENV_LATE
 #undef LLE_LOAD_STATE
@@ -881,12 +915,12 @@ __global__ void __launch_bounds__(256, (G >= 8 ? 3 : 4)) step_kernel(BatchPtrs P
 #undef LLE_ROT_L
 #undef LLE_ET
 #undef LLE_PITCH
-    }
     if (CNT_LDS && env_ok && a == 0) {
         cnt.steps = cnt_lds[0]; cnt.gems = cnt_lds[1]; cnt.exits = cnt_lds[2]; cnt.died = cnt_lds[3];
         cnt.invalid = cnt_lds[4]; cnt.resets = cnt_lds[5]; cnt.bonus = cnt_lds[6];
     }
-    flush_stats(P.stats, HEAD ? unpark_uniform(pk_wave) : wave_id, cnt, A, lane, PRE_STATS, stats_old);
+    if (ROLL) flush_stats(P.stats, wave_id, cnt, A, lane);
+    else if (!PRE_STATS || !TAIL_IN_POST) flush_stats_packed(P.stats, HEAD ? unpark_uniform(pk_wave) : wave_id, cnt_reward, cnt_flags, A, lane, PRE_STATS, stats_old);
     if (STAMPED && stamps) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         LLE_STAMP(6);

@@ -55,6 +55,22 @@ LLE_HD uint32_t action_hash_pair(uint64_t key, uint64_t env, uint32_t pair) {
 }
 LLE_HD uint32_t action_field(uint32_t pair_hash, uint32_t agent) { return (pair_hash >> (16u * (agent & 1u))) & 0xFFFFu; }
 
+// ---- the counters of a step (LLE_BUF_STATS), and their packed form.  A SINGLE step of one environment fits into two words of 8-bit
+// fields: the reward word as LLE_BUF_REWARD holds it, n_gem | n_exit << 8 | n_died << 16 | bonus << 24, and steps | invalid << 8 |
+// resets << 16.  A wavefront sums the two words over its lead lanes instead of seven counters (kernel_common.hpp flush_stats_packed); a
+// field of the sum must stay below 256, or it carries into its neighbour: stat_fields_fit is the bound, checked at compile time where
+// the sum is taken.  (Fused rollouts accumulate over n_steps and keep 32-bit sums.)
+struct StepCounts { uint32_t steps, gems, exits, died, invalid, resets, bonus; };
+constexpr uint32_t STAT_FIELD_MAX = 255u;
+LLE_HD uint32_t stat_pack_reward(uint32_t n_gem, uint32_t n_exit, uint32_t n_died, uint32_t bonus) { return n_gem | (n_exit << 8) | (n_died << 16) | (bonus << 24); }
+LLE_HD uint32_t stat_pack_flags(uint32_t steps, uint32_t invalid, uint32_t resets) { return steps | (invalid << 8) | (resets << 16); }
+LLE_HD StepCounts stat_unpack(uint32_t reward_sum, uint32_t flags_sum) {
+    return StepCounts{flags_sum & 0xFFu, reward_sum & 0xFFu, (reward_sum >> 8) & 0xFFu, (reward_sum >> 16) & 0xFFu,
+                      (flags_sum >> 8) & 0xFFu, (flags_sum >> 16) & 0xFFu, reward_sum >> 24};
+}
+// `n_envs` environments summed, no field of any of them above `per_env_max`
+constexpr bool stat_fields_fit(uint32_t n_envs, uint32_t per_env_max) { return n_envs * per_env_max <= STAT_FIELD_MAX; }
+
 LLE_HD uint32_t popc5(uint32_t m) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return (uint32_t)__popc(m);
